@@ -137,6 +137,36 @@ def cpu_baseline(backbone, weights, n_sample):
 
 
 # ------------------------------------------------------------------------------------------ launcher
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, poses, rec, extras):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  Pose fields and the (gathered) pose records are written whole in
+    float64 (R, t exact; the integer fields exactly representable).  The per-detection masks of --masks are far larger than the budget:
+    a fixed, seeded sample of their flattened elements (the same indices for the same shape) goes out as float32."""
+    from pix2pose_amd import _lib
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(poses)
+    v = np.frombuffer((_lib.Pose * max(n, 1))(*poses), dtype=_lib.POSE_DTYPE, count=n)
+    arrays = {"pose_R": v["R"].reshape(n, 3, 3), "pose_t": v["t"]}
+    for f in ("frac_inlier", "n_inliers", "n_init_mask", "status", "best_slot", "bbox_t", "n_candidates", "ransac_iters"):
+        arrays["pose_" + f] = v[f]
+    arrays["pose_records"] = rec
+    arrays = {k: np.asarray(a, np.float64) for k, a in arrays.items()}
+    masks = [k for k in ("valid_mask", "img_pred") if extras and k in extras]
+    budget = (DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - (1 << 20)) // max(len(masks), 1) // 4
+    for k in masks:
+        a = extras[k].reshape(-1)
+        if a.size > budget:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, budget, replace=False))
+            a = a[idx]
+        arrays[k] = a.astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _self_launch(n):
     """`python bench.py --gpus N` from a plain shell: start N ranks of this script under torch.distributed.run
     (one process per GPU, rendezvous on 127.0.0.1) and become that launcher."""
@@ -190,7 +220,12 @@ def main():
                     "e.g. 40,300 for general crop sizes -- profiling runs)")
     ap.add_argument("--batch64", type=int, default=20, help="passes of the configs[1] leg (64-input generator forward only, N=1; 0 = skip)")
     ap.add_argument("--no-legs", action="store_true", help="skip the f32 / host-frame / latency / CPU legs (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what the timed path returned in its last step as DIR/<name>.npy (float64 pose fields and records, "
+                         "a fixed float32 sample of valid_mask / img_pred with --masks; at most 64 MB in all) for output-for-output comparison of two builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_legs:
         args.f32_steps = args.host_frames = args.latency = args.cpu_sample = args.general = args.batch64 = 0
     if args.host_frames < 0:
@@ -275,6 +310,7 @@ def main():
             comm.close()
             comm, comm_note = None, "torch.distributed (another rank could not create the C ABI communicator)"
     submit_s = []           # host seconds inside every est_pose_submit call (marshalling + enqueueing one batch)
+    last_extras = [None]    # optional outputs (valid_mask / img_pred) of the batch collected last
     gather_q = []           # all-gathers in flight: started when a step is collected, waited for one step later
 
     def finish(poses, last=False):
@@ -300,7 +336,8 @@ def main():
         out = None
         if blocking:
             for i in range(k):
-                out = finish(est_pose_batch(ctx, specs, imgs(i), dets, want_masks=masks, anti_aliasing=aa, **kw)[0], last=i == k - 1)
+                p, last_extras[0] = est_pose_batch(ctx, specs, imgs(i), dets, want_masks=masks, anti_aliasing=aa, **kw)
+                out = finish(p, last=i == k - 1)
             return out
         pending = []
         for i in range(k):
@@ -315,6 +352,7 @@ def main():
         return out
 
     def collect(pb, last=False):
+        last_extras[0] = pb.extras
         if comm is None:
             return finish(pb.collect(), last=last)
         poses, allp = pb.collect_gathered(comm, args.batch)
@@ -348,6 +386,7 @@ def main():
     poses, rec = run_steps(args.steps)
     barrier()
     dt = time.perf_counter() - t0
+    timed_extras = last_extras[0]
     if args.blocking:
         stats = ctx.profile_read(reset=True)
         ctx.profile(False)
@@ -672,6 +711,8 @@ def main():
         out["pose_delta_vs_oracle_max_mm_deg"] = [out["pose_delta_vs_oracle"]["max_dt_mm"], out["pose_delta_vs_oracle"]["max_drot_deg"]]
     elif rank == 0:
         out["cpu_baseline"] = None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, poses, rec, timed_extras)
     if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()

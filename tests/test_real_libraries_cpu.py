@@ -3,8 +3,6 @@
 re-derives the committed fixtures from the libraries themselves instead of trusting a file:
 
   * tests/golden/external_vectors.json ["resize"]            == tools/make_external_vectors.py run now
-  * tests/golden/reference_est_pose_skimage018.json          == tests/golden/make_reference_vectors.py --real-skimage run now
-    (needs /root/reference, i.e. the build container; the GPU box has no reference checkout)
   * tests/test_convert_keras.py::test_read_hdf5_on_real_files under python3.9 (real h5py files; skipped under python3.10)
 
 Skipped where that interpreter is missing."""
@@ -50,68 +48,6 @@ def test_committed_resize_vectors_are_what_the_real_skimage_produces(tmp_path):
             for k in ("out_dtype", "u8_crc", "lt02_crc", "gt09_crc"):
                 assert a[k] == b[k], (k, a["n_in"], a["n_out"], a["dtype"])
         assert abs(a["sum"] - b["sum"]) < 1e-9 * max(1.0, abs(b["sum"]))
-
-
-@pytest.mark.skipif(not _have("skimage") or not os.path.isdir("/root/reference"), reason="needs the conda interpreter and /root/reference")
-def test_committed_est_pose_vectors_are_what_the_reference_produces_with_the_real_skimage():
-    """The exact-matrix scenes are re-derived and must be IDENTICAL to the committed ones on any machine (nothing in them goes through LAPACK).
-    The as-installed scenes depend on the BLAS kernels numpy selects for the CPU at hand (that is the point of the fixture's "cores" record), so
-    a fresh as-installed run is only held to what every machine shares: status, boxes, and byte-identity for most detections."""
-    keys = ("ok", "bbox_t", "mask_sum", "mask_crc", "img_pred_crc", "frac_inlier", "R", "t")
-    committed = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_est_pose_skimage018.json")))
-    r = _run([os.path.join("tests", "golden", "make_reference_vectors.py"), "--real-skimage", "--scenes-only", "--exact-matrix"])
-    assert r.returncode == 0, r.stderr[-2000:]
-    fresh = json.loads(r.stdout.strip().splitlines()[-1])
-    n = 0
-    for sf, sc in zip(fresh, committed["scenes_exact_matrix"]):
-        for df, dc in zip(sf["dets"], sc["dets"]):
-            assert [df.get(k) for k in keys] == [dc.get(k) for k in keys]
-            n += 1
-    assert n >= 30
-    r = _run([os.path.join("tests", "golden", "make_reference_vectors.py"), "--real-skimage", "--scenes-only"])
-    assert r.returncode == 0, r.stderr[-2000:]
-    fresh = json.loads(r.stdout.strip().splitlines()[-1])
-    same = tot = 0
-    for sf, sc in zip(fresh, committed["scenes_exact_matrix"]):
-        for df, dc in zip(sf["dets"], sc["dets"]):
-            assert df["ok"] == dc["ok"] and df["bbox_t"] == dc["bbox_t"]
-            tot += 1
-            same += all(df.get(k) == dc.get(k) for k in ("mask_sum", "mask_crc", "img_pred_crc", "frac_inlier"))
-    assert same >= 0.85 * tot, (same, tot)
-
-
-@pytest.mark.skipif(not _have("skimage") or not os.path.isdir("/root/reference"), reason="needs the conda interpreter and /root/reference")
-def test_committed_skimage015_vectors_are_what_the_real_libraries_produce():
-    """tests/golden/reference_est_pose_skimage015.json (the 0.15 / 0.16 resize generation: REAL scipy gaussian_filter on every image as
-    passed -- bool keep mask included --, then the REAL scikit-image 0.18.3 float64 warp with the exact affine map) re-derived now."""
-    keys = ("ok", "bbox_t", "mask_sum", "mask_crc", "img_pred_crc", "frac_inlier", "R", "t")
-    committed = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_est_pose_skimage015.json")))
-    r = _run([os.path.join("tests", "golden", "make_reference_vectors.py"), "--skimage015", "--scenes-only"])
-    assert r.returncode == 0, r.stderr[-2000:]
-    fresh = json.loads(r.stdout.strip().splitlines()[-1])
-    n = 0
-    for sf, sc in zip(fresh, committed["scenes"]):
-        for df, dc in zip(sf["dets"], sc["dets"]):
-            assert [df.get(k) for k in keys] == [dc.get(k) for k in keys]
-            n += 1
-    assert n >= 25
-
-
-@pytest.mark.skipif(not _have("skimage") or not os.path.isdir("/root/reference"), reason="needs the conda interpreter and /root/reference")
-def test_committed_skimage014_vectors_are_what_the_real_library_produces():
-    """tests/golden/reference_est_pose_skimage014.json (the <= 0.14 resize generation = the library's default: every resize call site of the
-    reference's est_pose served by the REAL scikit-image 0.18.3 float64 warp without a filter, exact affine map) re-derived now."""
-    keys = ("ok", "bbox_t", "mask_sum", "mask_crc", "img_pred_crc", "frac_inlier", "R", "t")
-    committed = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_est_pose_skimage014.json")))
-    r = _run([os.path.join("tests", "golden", "make_reference_vectors.py"), "--skimage014", "--scenes-only"])
-    assert r.returncode == 0, r.stderr[-2000:]
-    fresh = json.loads(r.stdout.strip().splitlines()[-1])
-    n = 0
-    for sf, sc in zip(fresh, committed["scenes"]):
-        for df, dc in zip(sf["dets"], sc["dets"]):
-            assert [df.get(k) for k in keys] == [dc.get(k) for k in keys]
-            n += 1
-    assert n >= 25
 
 
 def test_bool_mask_filter_restatement_equals_scipy():
