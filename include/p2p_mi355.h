@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define P2P_ABI_VERSION 9
+#define P2P_ABI_VERSION 10
 
 /* The library is built with -fvisibility=hidden: the entry points declared here (P2P_API) are its ONLY dynamic symbols
  * (tests/test_host_cpu.py holds `nm -D` to exactly this list). */
@@ -57,7 +57,7 @@ typedef struct {
 P2P_API int p2p_abi_version(void);
 /* Binding self-checks: sizeof() of the public structs as this build of the library sees them
  * (which: 0 p2p_tensor, 1 p2p_image, 2 p2p_object, 3 p2p_detection, 4 p2p_pose, 5 p2p_est_pose_opts,
- * 6 p2p_kernel_stats; -1 otherwise), and the hash of the sources the library was built from
+ * 6 p2p_kernel_stats, 7 p2p_refine_job, 8 p2p_depth_score; -1 otherwise), and the hash of the sources the library was built from
  * (pix2pose_amd/build.py) -- a foreign-language binding compares both with its own declarations / tree
  * before the first call, so that a stale .so is an error and not a silent struct mismatch. */
 P2P_API int p2p_abi_sizeof(int which);
@@ -410,6 +410,54 @@ P2P_API int p2p_profile_enable(p2p_ctx* ctx, int on);
 /* Harvest finished events (synchronises the stream) and return the accumulated stats; reset
  * clears the accumulators afterwards.  stats must hold P2P_PROFILE_SLOTS entries. */
 P2P_API int p2p_profile_read(p2p_ctx* ctx, p2p_kernel_stats* stats, int reset);
+
+/* ------------------------------------------------------------------------------------------
+ * Depth path (RGB-D scoring, reference tools/5_evaluation_bop_icp3d.py).  csrc/depth.hip; DESIGN.md section 8.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p2p_mesh p2p_mesh;   /* one object's triangle mesh, vertices in HBM */
+
+/* Upload a mesh (reference: rendering/model.py Model3D.load, and pix2pose_amd/mesh.py read_ply): verts_mm [n_verts][3] in mm
+ * (the library stores them in metres, like Model3D.load(scale=0.001)), tris [n_tris][3] vertex indices (host pointers).  An index
+ * outside [0, n_verts) is P2P_ERR_INVALID_ARG. */
+P2P_API int p2p_mesh_create(p2p_ctx* ctx, const float* verts_mm, int n_verts, const int* tris, int n_tris, p2p_mesh** out);
+P2P_API void p2p_mesh_destroy(p2p_mesh* mesh);
+
+/* One detection of the depth path, in the units of p2p_pose: mesh meshes[mesh_idx] at pose (R, t) through camK, t in mm.  The
+ * library hands t/1000 to the rasteriser like icp3d.py passes tra_pred/1000 to render_obj(), and keeps render_obj's unit quirk on
+ * that value (:46: tra[2] > 100 m is taken as mm and divided by 1000 once more).  img_idx indexes the depth images of
+ * p2p_depth_score_batch (ignored by p2p_render_depth_batch); union_mask is a host u8 [height*width] (nonzero = in the union mask,
+ * p2p_depth_score_batch only).  This is the job record the depth refinement entry point (ICP, not built yet) is to take as well. */
+typedef struct {
+    int img_idx;
+    int mesh_idx;
+    double camK[9];
+    double R[9];
+    double t[3];
+    const unsigned char* union_mask;
+} p2p_refine_job;
+
+/* Depth-only z-buffer (replaces render_obj(), icp3d.py:40-50, and rendering/renderer_xyz.py Renderer): depth [n_jobs][height][width]
+ * float32 in metres, 0 where nothing is drawn (host pointer).  Nearest surface, coverage at pixel centres (u, v) = (i + 0.5, j + 0.5),
+ * 1/z interpolated in screen space, near / far clip 0.01 / 10 m, back faces culled; the coverage rule is in DESIGN.md section 8.
+ * Deterministic: the result does not depend on triangle order or on the other jobs of the batch. */
+P2P_API int p2p_render_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs,
+                                   int height, int width, float* depth);
+
+/* Depth agreement of a detection (icp3d.py:470-490, fcn() at :314-315): renders job j as above and compares it with the sensor depth
+ * depth_images[job.img_idx] (host float32 [height][width], metres: the caller applies depth_scale, icp3d.py:360) over the union mask:
+ * diff = |depth_ref - depth_t|, inlier_count = sum(diff < 0.02), fcn = sum(max(0, 0.02 - diff)) / 0.02, ratio = inlier_count / union.
+ * inlier_masks (may be null): host u8 [n_jobs][height][width], 1 where in the union mask and diff < 0.02.  fcn is summed in a fixed
+ * order, so a job's score is bit-identical alone or in a batch.  The caller forms the score (det_score * fcn in the first round). */
+typedef struct {
+    int64_t inlier_count;
+    int64_t union_count;
+    double fcn;
+    double ratio;        /* inlier_count / union_count (0 when the union is empty) */
+} p2p_depth_score;
+
+P2P_API int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                                  int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_depth_score* out,
+                                  unsigned char* inlier_masks);
 
 #ifdef __cplusplus
 }

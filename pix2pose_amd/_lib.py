@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("P2P_LIB", os.path.join(_HERE, "libp2p_mi355.so"))     # P2P_LIB: development override
 
 P2P_OK = 0
-ABI_VERSION = 9            # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
+ABI_VERSION = 10           # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
 MAX_RANSAC_ITERATIONS = 128
 BACKBONE = {"paper": 0, "resnet50": 1}
 PRECISION = {"f32": 0, "f16x3": 1, "auto": 2}     # p2p_precision; "auto" = split-f16 with an fp32 twin it falls back to on a range event
@@ -108,6 +108,15 @@ class KernelStats(C.Structure):
     _fields_ = [("launches", C.c_int64), ("total_ms", C.c_double), ("algo_flops", C.c_double), ("algo_bytes", C.c_double)]
 
 
+class RefineJob(C.Structure):
+    _fields_ = [("img_idx", C.c_int), ("mesh_idx", C.c_int), ("camK", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3),
+                ("union_mask", C.c_void_p)]
+
+
+class DepthScore(C.Structure):
+    _fields_ = [("inlier_count", C.c_int64), ("union_count", C.c_int64), ("fcn", C.c_double), ("ratio", C.c_double)]
+
+
 _lib = None
 
 
@@ -171,7 +180,7 @@ def _stale_reason_of(L):
             return "built from other sources (build id %s, tree %s)" % (got, want)
     L.p2p_abi_sizeof.restype = C.c_int
     L.p2p_abi_sizeof.argtypes = [C.c_int]
-    for which, typ in enumerate((Tensor, Image, Object, Detection, Pose, EstPoseOpts, KernelStats)):
+    for which, typ in enumerate((Tensor, Image, Object, Detection, Pose, EstPoseOpts, KernelStats, RefineJob, DepthScore)):
         if L.p2p_abi_sizeof(which) != C.sizeof(typ):
             return "sizeof(%s) = %d in the library, %d in the binding" % (typ.__name__, L.p2p_abi_sizeof(which), C.sizeof(typ))
     return None
@@ -239,6 +248,12 @@ def lib():
     dp = C.POINTER(C.c_double)
     L.p2p_pnp_ransac_batch.argtypes = [vp, dp, dp, dp, C.POINTER(ci), ci, ci, C.c_double, C.c_double, dp, dp,
                                        C.POINTER(ci), C.POINTER(ci), vp]
+    L.p2p_mesh_create.argtypes = [vp, vp, ci, vp, ci, C.POINTER(vp)]
+    L.p2p_mesh_destroy.argtypes = [vp]
+    L.p2p_mesh_destroy.restype = None
+    L.p2p_render_depth_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci, vp]
+    L.p2p_depth_score_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
+                                        C.POINTER(DepthScore), vp]
     _lib = L
     return L
 

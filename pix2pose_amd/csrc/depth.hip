@@ -1,0 +1,407 @@
+// Depth path of the RGB-D evaluation (reference tools/5_evaluation_bop_icp3d.py): meshes in HBM, a depth-only z-buffer
+// (render_obj(), :40-50, through rendering/renderer_xyz.py) and the depth-agreement score of a detection (:470-490).
+// The exact rules (projection, coverage, ties, clipping, culling) are written down in DESIGN.md section 8; tests/depth_ref.py
+// restates them in float64 numpy.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "model.h"
+#include "pipeline.h"
+
+#pragma clang fp contract(off)     // no FMA contraction: the restatement evaluates the same expressions in the same order
+
+struct p2p_mesh {
+    int device = 0;
+    int n_verts = 0, n_tris = 0;
+    float* verts = nullptr;   // [n_verts][3] metres (float32, like Model3D.load(scale=0.001))
+    int* tris = nullptr;      // [n_tris][3], every index checked against n_verts at creation
+};
+
+namespace p2p {
+
+namespace {
+
+#define DEPTH_TRY(expr)                                                                       \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return P2P_ERR_HIP;                                                               \
+        }                                                                                     \
+    } while (0)
+
+constexpr double CLIP_NEAR = 0.01, CLIP_FAR = 10.0;      // Renderer.set_cam defaults (renderer_xyz.py:126)
+constexpr unsigned DEPTH_EMPTY = 0x7f800000u;            // +inf: above every finite depth in the atomicMin order of positive floats
+constexpr int RASTER_THREADS = 256, SCORE_THREADS = 256;
+
+// One job as the device sees it: the mesh's arrays, the pose in metres (unit quirk applied), the intrinsics.
+struct RasterJob {
+    const float* verts;
+    const int* tris;
+    int n_tris;
+    double R[9], t[3];
+    double fx, s, cx, fy, cy;
+};
+
+// Edge function of a -> b at p, and the owner rule for a sample exactly on the edge: with the triangle ordered so that
+// its area is positive, an edge owns its ties when it runs towards +v, or along v = const towards -u.  The two triangles sharing an
+// edge traverse it in opposite directions, so exactly one of them owns a tie.
+__device__ __forceinline__ double edge_fn(double au, double av, double bu, double bv, double pu, double pv)
+{
+    return (bu - au) * (pv - av) - (bv - av) * (pu - au);
+}
+__device__ __forceinline__ bool edge_in(double e, double au, double av, double bu, double bv)
+{
+    const double dv = bv - av, du = bu - au;
+    return e > 0.0 || (e == 0.0 && (dv > 0.0 || (dv == 0.0 && du < 0.0)));
+}
+
+// Triangle set-up shared by both routes: project, cull, clip; on success the vertices are ordered for a positive area A and
+// [i0, i1] x [j0, j1] is the pixel box clamped to the image (every index formed from it is in bounds).
+struct TriSetup {
+    double u[3], v[3], z[3], A;
+    int i0, i1, j0, j1;
+};
+
+__device__ __forceinline__ bool tri_setup(const RasterJob& J, int f, int H, int W, TriSetup& T)
+{
+    for (int k = 0; k < 3; ++k) {
+        const float* p = J.verts + 3 * (size_t)J.tris[3 * (size_t)f + k];
+        const double X = p[0], Y = p[1], Z = p[2];
+        const double xc = J.R[0] * X + J.R[1] * Y + J.R[2] * Z + J.t[0];
+        const double yc = J.R[3] * X + J.R[4] * Y + J.R[5] * Z + J.t[1];
+        const double zc = J.R[6] * X + J.R[7] * Y + J.R[8] * Z + J.t[2];
+        if (!(zc >= CLIP_NEAR)) return false;      // straddles / lies before the near plane (or NaN): rejected whole
+        T.u[k] = J.fx * (xc / zc) + J.s * (yc / zc) + J.cx;
+        T.v[k] = J.fy * (yc / zc) + J.cy;
+        T.z[k] = zc;
+        if (!(fabs(T.u[k]) < 1e9 && fabs(T.v[k]) < 1e9)) return false;
+    }
+    // front faces have a negative area in (u, v) (v down): counter-clockwise in the flipped GL window; back faces and
+    // degenerate triangles are not drawn.  Swapping vertices 1 and 2 makes the area positive for the edge functions.
+    const double area = (T.u[1] - T.u[0]) * (T.v[2] - T.v[0]) - (T.u[2] - T.u[0]) * (T.v[1] - T.v[0]);
+    if (!(area < 0.0)) return false;
+    double t_;
+    t_ = T.u[1]; T.u[1] = T.u[2]; T.u[2] = t_;
+    t_ = T.v[1]; T.v[1] = T.v[2]; T.v[2] = t_;
+    t_ = T.z[1]; T.z[1] = T.z[2]; T.z[2] = t_;
+    T.A = -area;
+    const double umin = fmin(T.u[0], fmin(T.u[1], T.u[2])), umax = fmax(T.u[0], fmax(T.u[1], T.u[2]));
+    const double vmin = fmin(T.v[0], fmin(T.v[1], T.v[2])), vmax = fmax(T.v[0], fmax(T.v[1], T.v[2]));
+    T.i0 = (int)fmax(0.0, ceil(umin - 0.5)); T.i1 = (int)fmin((double)(W - 1), floor(umax - 0.5));
+    T.j0 = (int)fmax(0.0, ceil(vmin - 0.5)); T.j1 = (int)fmin((double)(H - 1), floor(vmax - 0.5));
+    return T.i0 <= T.i1 && T.j0 <= T.j1;
+}
+
+// One pixel centre of a set-up triangle: coverage with the tie rule, 1/z interpolation, far clip, atomicMin on the float bits.
+__device__ __forceinline__ void tri_pixel(const TriSetup& T, int i, int j, unsigned* zrow_base, int W)
+{
+    const double pu = i + 0.5, pv = j + 0.5;
+    const double e0 = edge_fn(T.u[1], T.v[1], T.u[2], T.v[2], pu, pv);
+    const double e1 = edge_fn(T.u[2], T.v[2], T.u[0], T.v[0], pu, pv);
+    const double e2 = edge_fn(T.u[0], T.v[0], T.u[1], T.v[1], pu, pv);
+    if (!(edge_in(e0, T.u[1], T.v[1], T.u[2], T.v[2]) && edge_in(e1, T.u[2], T.v[2], T.u[0], T.v[0]) &&
+          edge_in(e2, T.u[0], T.v[0], T.u[1], T.v[1])))
+        return;
+    const double iz = (e0 / T.A) / T.z[0] + (e1 / T.A) / T.z[1] + (e2 / T.A) / T.z[2];
+    const double d = 1.0 / iz;
+    if (!(d >= CLIP_NEAR && d <= CLIP_FAR)) return;
+    atomicMin(zrow_base + (size_t)j * W + i, __float_as_uint((float)d));
+}
+
+// Route 1: one thread per triangle (blockIdx.y = job) walks its pixel box when the box holds at most BIG_TRI_PIXELS centres;
+// larger triangles (near the camera, coarse meshes) are appended to `big` for route 2, so no thread walks a large box alone.
+constexpr int BIG_TRI_PIXELS = 1024;
+__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_kernel(const RasterJob* __restrict__ jobs, unsigned* __restrict__ zbuf,
+                                                                      int H, int W, int2* __restrict__ big, unsigned* __restrict__ n_big)
+{
+    const RasterJob& J = jobs[blockIdx.y];
+    const int f = blockIdx.x * RASTER_THREADS + threadIdx.x;
+    if (f >= J.n_tris) return;
+    TriSetup T;
+    if (!tri_setup(J, f, H, W, T)) return;
+    if ((int64_t)(T.i1 - T.i0 + 1) * (T.j1 - T.j0 + 1) > BIG_TRI_PIXELS) {
+        big[atomicAdd(n_big, 1u)] = make_int2((int)blockIdx.y, f);      // at most one entry per (job, triangle): within capacity
+        return;
+    }
+    unsigned* zb = zbuf + (size_t)blockIdx.y * H * W;
+    for (int j = T.j0; j <= T.j1; ++j)
+        for (int i = T.i0; i <= T.i1; ++i) tri_pixel(T, i, j, zb, W);
+}
+
+// Route 2: one workgroup per large triangle, its threads striding over the pixel box.  The list order depends on scheduling;
+// the result does not (atomicMin), so both routes together stay deterministic.
+__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_big_kernel(const RasterJob* __restrict__ jobs, unsigned* __restrict__ zbuf,
+                                                                          int H, int W, const int2* __restrict__ big,
+                                                                          const unsigned* __restrict__ n_big)
+{
+    const unsigned n = *n_big;
+    for (unsigned e = blockIdx.x; e < n; e += gridDim.x) {
+        const int2 jf = big[e];
+        TriSetup T;
+        if (!tri_setup(jobs[jf.x], jf.y, H, W, T)) continue;     // same set-up as route 1: succeeds
+        unsigned* zb = zbuf + (size_t)jf.x * H * W;
+        const int bw = T.i1 - T.i0 + 1;
+        const int64_t npix = (int64_t)bw * (T.j1 - T.j0 + 1);
+        for (int64_t q = threadIdx.x; q < npix; q += RASTER_THREADS) tri_pixel(T, T.i0 + (int)(q % bw), T.j0 + (int)(q / bw), zb, W);
+    }
+}
+
+__global__ void depth_finish_kernel(unsigned* __restrict__ zbuf, size_t n)
+{
+    for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x)
+        if (zbuf[k] == DEPTH_EMPTY) zbuf[k] = 0u;        // +0.0f
+}
+
+// One workgroup per job.  Thread k takes pixels k, k + 256, ...; its partial sums are combined by a fixed tree, so the result of a
+// job depends on nothing but its own inputs.
+__global__ void __launch_bounds__(SCORE_THREADS) depth_score_kernel(const float* __restrict__ ref, const float* __restrict__ images,
+                                                                    const int* __restrict__ img_of, const unsigned char* __restrict__ masks,
+                                                                    int HW, unsigned char* __restrict__ inl_out,
+                                                                    p2p_depth_score* __restrict__ out)
+{
+    __shared__ double s_fcn[SCORE_THREADS];
+    __shared__ long long s_in[SCORE_THREADS], s_un[SCORE_THREADS];
+    const int j = blockIdx.x;
+    const float* dr = ref + (size_t)j * HW;
+    const float* dt = images + (size_t)img_of[j] * HW;
+    const unsigned char* m = masks + (size_t)j * HW;
+    double fcn = 0.0;
+    long long inl = 0, un = 0;
+    for (int p = threadIdx.x; p < HW; p += SCORE_THREADS) {
+        unsigned char keep = 0;
+        if (m[p]) {
+            ++un;
+            const double diff = fabs((double)dr[p] - (double)dt[p]);
+            if (diff < 0.02) { ++inl; keep = 1; }
+            fcn += fmax(0.0, 0.02 - diff) / 0.02;
+        }
+        if (inl_out) inl_out[(size_t)j * HW + p] = keep;
+    }
+    s_fcn[threadIdx.x] = fcn; s_in[threadIdx.x] = inl; s_un[threadIdx.x] = un;
+    __syncthreads();
+    for (int w = SCORE_THREADS / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            s_fcn[threadIdx.x] += s_fcn[threadIdx.x + w];
+            s_in[threadIdx.x] += s_in[threadIdx.x + w];
+            s_un[threadIdx.x] += s_un[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[j].inlier_count = s_in[0];
+        out[j].union_count = s_un[0];
+        out[j].fcn = s_fcn[0];
+        out[j].ratio = s_un[0] > 0 ? (double)s_in[0] / (double)s_un[0] : 0.0;
+    }
+}
+
+int check_jobs(const char* who, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W,
+               int n_images)
+{
+    if (H <= 0 || W <= 0 || (int64_t)H * W > (1 << 26)) {
+        set_error("%s: bad image size %d x %d", who, H, W);
+        return P2P_ERR_INVALID_ARG;
+    }
+    for (int j = 0; j < n_jobs; ++j) {
+        const p2p_refine_job& J = jobs[j];
+        if (J.mesh_idx < 0 || J.mesh_idx >= n_meshes || !meshes[J.mesh_idx]) {
+            set_error("%s: job %d names mesh %d of %d", who, j, J.mesh_idx, n_meshes);
+            return P2P_ERR_INVALID_ARG;
+        }
+        if (n_images >= 0 && (J.img_idx < 0 || J.img_idx >= n_images || !J.union_mask)) {
+            set_error("%s: job %d: image %d of %d, union_mask %p", who, j, J.img_idx, n_images, (const void*)J.union_mask);
+            return P2P_ERR_INVALID_ARG;
+        }
+    }
+    return P2P_OK;
+}
+
+// Renders every job into zbuf [n_jobs][H][W] (device, float bits), 0 where nothing is drawn.
+int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, unsigned* zbuf, DevBuf& djobs)
+{
+    hipStream_t st = X.stream;
+    std::vector<RasterJob> rj(n_jobs);
+    int max_tris = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const p2p_refine_job& J = jobs[j];
+        const p2p_mesh* M = meshes[J.mesh_idx];
+        if (M->device != X.device) {
+            set_error("p2p depth: mesh %d lives on device %d, the context on device %d", J.mesh_idx, M->device, X.device);
+            return P2P_ERR_INVALID_ARG;
+        }
+        RasterJob& r = rj[j];
+        r.verts = M->verts; r.tris = M->tris; r.n_tris = M->n_tris;
+        for (int k = 0; k < 9; ++k) r.R[k] = J.R[k];
+        double tm[3];
+        for (int k = 0; k < 3; ++k) tm[k] = J.t[k] / 1000.0;            // icp3d.py: render_obj(..., tra_pred/1000, ...)
+        const bool quirk = tm[2] > 100.0;                               // render_obj: if(tra[2]>100): tra = tra/1000
+        for (int k = 0; k < 3; ++k) r.t[k] = quirk ? tm[k] / 1000.0 : tm[k];
+        r.fx = J.camK[0]; r.s = J.camK[1]; r.cx = J.camK[2]; r.fy = J.camK[4]; r.cy = J.camK[5];
+        max_tris = std::max(max_tris, M->n_tris);
+    }
+    int rc;
+    // job records, then the large-triangle counter and list (capacity: every (job, triangle) pair once)
+    const size_t cap = (size_t)n_jobs * std::max(max_tris, 1);
+    const size_t jb = (sizeof(RasterJob) * n_jobs + 255) / 256 * 256;
+    if ((rc = djobs.reserve(jb + 256 + sizeof(int2) * cap))) return rc;
+    RasterJob* dj = djobs.as<RasterJob>();
+    unsigned* n_big = reinterpret_cast<unsigned*>(djobs.as<char>() + jb);
+    int2* big = reinterpret_cast<int2*>(djobs.as<char>() + jb + 256);
+    const size_t n = (size_t)n_jobs * H * W;
+    DEPTH_TRY(hipMemcpyAsync(dj, rj.data(), sizeof(RasterJob) * n_jobs, hipMemcpyHostToDevice, st));
+    DEPTH_TRY(hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
+    DEPTH_TRY(hipMemsetD32Async((hipDeviceptr_t)zbuf, (int)DEPTH_EMPTY, n, st));
+    if (max_tris > 0) {
+        dim3 grid((max_tris + RASTER_THREADS - 1) / RASTER_THREADS, n_jobs);
+        depth_raster_kernel<<<grid, RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
+        DEPTH_TRY(hipGetLastError());
+        depth_raster_big_kernel<<<(unsigned)std::min<size_t>(cap, 1024), RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
+        DEPTH_TRY(hipGetLastError());
+    }
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
+    depth_finish_kernel<<<blocks, 256, 0, st>>>(zbuf, n);
+    DEPTH_TRY(hipGetLastError());
+    return P2P_OK;
+}
+
+}  // namespace
+}  // namespace p2p
+
+using namespace p2p;
+
+extern "C" {
+
+int p2p_mesh_create(p2p_ctx* ctx, const float* verts_mm, int n_verts, const int* tris, int n_tris, p2p_mesh** out)
+{
+    if (!ctx || !out || n_verts <= 0 || n_tris < 0 || !verts_mm || (n_tris > 0 && !tris)) {
+        set_error("p2p_mesh_create: bad arguments");
+        return P2P_ERR_INVALID_ARG;
+    }
+    *out = nullptr;
+    for (int64_t k = 0; k < 3 * (int64_t)n_tris; ++k)
+        if (tris[k] < 0 || tris[k] >= n_verts) {
+            set_error("p2p_mesh_create: triangle %lld names vertex %d of %d", (long long)(k / 3), tris[k], n_verts);
+            return P2P_ERR_INVALID_ARG;
+        }
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    DEPTH_TRY(hipSetDevice(c->device));
+    std::vector<float> vm((size_t)n_verts * 3);
+    for (size_t k = 0; k < vm.size(); ++k) vm[k] = verts_mm[k] * 0.001f;     // float32 x float32, as numpy scales a float32 cloud
+    p2p_mesh* M = new p2p_mesh;
+    M->device = c->device; M->n_verts = n_verts; M->n_tris = n_tris;
+    hipError_t e = hipMalloc(&M->verts, vm.size() * 4);
+    if (e == hipSuccess) e = hipMalloc(&M->tris, std::max<size_t>(1, (size_t)n_tris * 3) * 4);
+    if (e == hipSuccess) e = hipMemcpy(M->verts, vm.data(), vm.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_tris > 0) e = hipMemcpy(M->tris, tris, (size_t)n_tris * 12, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        set_error("p2p_mesh_create: %s", hipGetErrorString(e));
+        p2p_mesh_destroy(M);
+        return P2P_ERR_HIP;
+    }
+    *out = M;
+    return P2P_OK;
+}
+
+void p2p_mesh_destroy(p2p_mesh* mesh)
+{
+    if (!mesh) return;
+    (void)hipSetDevice(mesh->device);
+    if (mesh->verts) (void)hipFree(mesh->verts);
+    if (mesh->tris) (void)hipFree(mesh->tris);
+    delete mesh;
+}
+
+int p2p_render_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int height,
+                           int width, float* depth)
+{
+    if (!ctx || n_jobs < 0 || (n_jobs > 0 && (!meshes || !jobs || !depth))) {
+        set_error("p2p_render_depth_batch: bad arguments");
+        return P2P_ERR_INVALID_ARG;
+    }
+    int rc;
+    if ((rc = check_jobs("p2p_render_depth_batch", meshes, n_meshes, jobs, n_jobs, height, width, -1))) return rc;
+    if (n_jobs == 0) return P2P_OK;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    DEPTH_TRY(hipSetDevice(c->device));
+    const size_t n = (size_t)n_jobs * height * width;
+    DevBuf dz, dj;
+    auto cleanup = [&]() { dz.release(); dj.release(); };
+    if ((rc = dz.reserve(n * 4)) || (rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) {
+        cleanup();
+        return rc;
+    }
+    hipError_t e;
+    if ((e = hipMemcpyAsync(depth, dz.p, n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        set_error("p2p_render_depth_batch: %s", hipGetErrorString(e));
+        cleanup();
+        return P2P_ERR_HIP;
+    }
+    cleanup();
+    return P2P_OK;
+}
+
+int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images, int n_images,
+                          const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_depth_score* out, unsigned char* inlier_masks)
+{
+    if (!ctx || n_jobs < 0 || n_images < 0 || (n_jobs > 0 && (!meshes || !jobs || !out || !depth_images))) {
+        set_error("p2p_depth_score_batch: bad arguments");
+        return P2P_ERR_INVALID_ARG;
+    }
+    int rc;
+    if ((rc = check_jobs("p2p_depth_score_batch", meshes, n_meshes, jobs, n_jobs, height, width, n_images))) return rc;
+    for (int i = 0; i < n_images; ++i)
+        if (!depth_images[i]) {
+            set_error("p2p_depth_score_batch: depth image %d is null", i);
+            return P2P_ERR_INVALID_ARG;
+        }
+    if (n_jobs == 0) return P2P_OK;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    DEPTH_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const size_t HW = (size_t)height * width;
+    DevBuf dz, dj, dimg, dmask, dof, dinl, dout;
+    auto cleanup = [&]() { dz.release(); dj.release(); dimg.release(); dmask.release(); dof.release(); dinl.release(); dout.release(); };
+    if ((rc = dz.reserve(n_jobs * HW * 4)) || (rc = dimg.reserve(n_images * HW * 4)) || (rc = dmask.reserve(n_jobs * HW)) ||
+        (rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
+        (inlier_masks && (rc = dinl.reserve(n_jobs * HW)))) {
+        cleanup();
+        return rc;
+    }
+    std::vector<int> img_of(n_jobs);
+    for (int j = 0; j < n_jobs; ++j) img_of[j] = jobs[j].img_idx;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n_images && e == hipSuccess; ++i)
+        e = hipMemcpyAsync(dimg.as<float>() + i * HW, depth_images[i], HW * 4, hipMemcpyHostToDevice, st);
+    for (int j = 0; j < n_jobs && e == hipSuccess; ++j)
+        e = hipMemcpyAsync(dmask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dof.p, img_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) {
+        set_error("p2p_depth_score_batch: %s", hipGetErrorString(e));
+        cleanup();
+        return P2P_ERR_HIP;
+    }
+    if ((rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) {
+        cleanup();
+        return rc;
+    }
+    depth_score_kernel<<<n_jobs, SCORE_THREADS, 0, st>>>(dz.as<float>(), dimg.as<float>(), dof.as<int>(), dmask.as<unsigned char>(),
+                                                         (int)HW, inlier_masks ? dinl.as<unsigned char>() : nullptr,
+                                                         dout.as<p2p_depth_score>());
+    if ((e = hipGetLastError()) != hipSuccess ||
+        (e = hipMemcpyAsync(out, dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (inlier_masks && (e = hipMemcpyAsync(inlier_masks, dinl.p, n_jobs * HW, hipMemcpyDeviceToHost, st)) != hipSuccess) ||
+        (e = hipStreamSynchronize(st)) != hipSuccess) {
+        set_error("p2p_depth_score_batch: %s", hipGetErrorString(e));
+        cleanup();
+        return P2P_ERR_HIP;
+    }
+    cleanup();
+    return P2P_OK;
+}
+
+}  // extern "C"

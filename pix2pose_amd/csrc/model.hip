@@ -1702,6 +1702,8 @@ int p2p_abi_sizeof(int which)
     case 4: return (int)sizeof(p2p_pose);
     case 5: return (int)sizeof(p2p_est_pose_opts);
     case 6: return (int)sizeof(p2p_kernel_stats);
+    case 7: return (int)sizeof(p2p_refine_job);
+    case 8: return (int)sizeof(p2p_depth_score);
     default: return -1;
     }
 }

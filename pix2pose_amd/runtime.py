@@ -431,3 +431,92 @@ def pnp_ransac_batch(ctx: Context, Ks, objs, imgs, iterations=100, reproj_err=5.
                                                mask.ctypes.data if want_mask else None), "p2p_pnp_ransac_batch")
     masks = [mask[offsets[i]:offsets[i + 1]] for i in range(n_prob)] if want_mask else None
     return ok.astype(bool), R.reshape(-1, 3, 3), t, info, masks
+
+
+class Mesh:
+    """An object's triangle mesh in HBM (p2p_mesh_create): verts [N,3] in mm (cast to float32), tris [M,3] vertex indices.
+    ``Mesh.from_ply(ctx, path)`` reads a BOP ``obj_<id:06d>.ply`` through pix2pose_amd.mesh.read_ply."""
+
+    def __init__(self, ctx: Context, verts, tris):
+        self.ctx = ctx
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+        self.n_verts, self.n_tris = len(v), len(f)
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p2p_mesh_create(ctx.handle, v.ctypes.data, len(v), f.ctypes.data, len(f), C.byref(self._h)),
+                   "p2p_mesh_create")
+
+    @classmethod
+    def from_ply(cls, ctx: Context, path: str) -> "Mesh":
+        from .mesh import read_ply
+        return cls(ctx, *read_ply(path))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            _lib.lib().p2p_mesh_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _depth_jobs(jobs, keep):
+    """jobs: sequence of dicts {mesh, camK [3,3], R [3,3], t [3] in mm (p2p_pose units), image, union_mask} -> p2p_refine_job[]."""
+    arr = (_lib.RefineJob * max(1, len(jobs)))()
+    for k, j in enumerate(jobs):
+        arr[k].mesh_idx = int(j["mesh"])
+        arr[k].img_idx = int(j.get("image", 0))
+        arr[k].camK[:] = [float(x) for x in np.asarray(j["camK"], np.float64).ravel()]
+        arr[k].R[:] = [float(x) for x in np.asarray(j["R"], np.float64).ravel()]
+        arr[k].t[:] = [float(x) for x in np.asarray(j["t"], np.float64).ravel()]
+        m = j.get("union_mask")
+        if m is not None:
+            m = np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8)
+            keep.append(m)
+            arr[k].union_mask = m.ctypes.data
+    return arr
+
+
+def render_depth_batch(ctx: Context, meshes, jobs, height: int, width: int):
+    """Depth-only z-buffer (p2p_render_depth_batch; replaces render_obj(), icp3d.py:40-50): float32 [n_jobs, H, W] in metres, 0 where
+    nothing is drawn.  jobs as in _depth_jobs (image / union_mask unused)."""
+    keep = []
+    arr = _depth_jobs(jobs, keep)
+    mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+    out = np.zeros((len(jobs), height, width), np.float32)
+    _lib.check(_lib.lib().p2p_render_depth_batch(ctx.handle, mh, len(meshes), arr, len(jobs), height, width, out.ctypes.data),
+               "p2p_render_depth_batch")
+    return out
+
+
+def depth_score_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = False):
+    """Depth agreement at each job's pose (p2p_depth_score_batch; icp3d.py:470-490): renders the job and compares it with
+    depths[job['image']] (float32 metres, depth_scale already applied) over job['union_mask'].  Returns a list of dicts
+    {inlier_count, union, fcn, ratio} and, with inlier_masks=True, a bool array [n_jobs, H, W] as well."""
+    depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+    if not depths:
+        raise ValueError("depth_score_batch needs at least one depth image")
+    H, W = depths[0].shape
+    if any(d.shape != (H, W) for d in depths):
+        raise ValueError("all depth images must have the same size")
+    for j in jobs:
+        if j.get("union_mask") is None or np.shape(j["union_mask"]) != (H, W):
+            raise ValueError("every job needs a union_mask of the depth images' size %r" % ((H, W),))
+    keep = []
+    arr = _depth_jobs(jobs, keep)
+    mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+    dp = (C.c_void_p * len(depths))(*[d.ctypes.data for d in depths])
+    res = (_lib.DepthScore * max(1, len(jobs)))()
+    masks = np.zeros((len(jobs), H, W), np.uint8) if inlier_masks else None
+    _lib.check(_lib.lib().p2p_depth_score_batch(ctx.handle, mh, len(meshes), dp, len(depths), arr, len(jobs), H, W, res,
+                                                masks.ctypes.data if masks is not None else None), "p2p_depth_score_batch")
+    out = [{"inlier_count": int(r.inlier_count), "union": int(r.union_count), "fcn": float(r.fcn), "ratio": float(r.ratio)}
+           for r in res[:len(jobs)]]
+    return (out, masks.astype(bool)) if inlier_masks else out
