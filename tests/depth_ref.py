@@ -3,6 +3,14 @@
 render_depth() follows the rules of p2p_render_depth_batch expression by expression (same operand order, no fused
 multiply-add), so where both cover a pixel the two depths agree to the last float32 bit but for the rare rounding tie;
 depth_score() restates icp3d.py:470-490.  Also the synthetic meshes the tests draw.
+
+Two oracles do not share that derivation: gl_window() / gl_readback_depth() are the reference's GL vertex transform and depth
+read-back as matrices (renderer_xyz.py:140-153,186-201, icp3d.py:40-50), and raycast_depth() is a ray caster in camera space.
+score_ref32() is the reference's score lines literally, in float32.
+
+NaN rule: a NaN sensor pixel inside the union mask counts in the union, is not an inlier and adds 0 to fcn (the kernel's
+fmax(0, 0.02 - diff)); depth_score() follows it with np.fmax.  The reference's np.maximum would make fcn NaN, but it only passes
+masks that exclude such pixels (depth_valid, icp3d.py:367,456).
 """
 import numpy as np
 
@@ -25,10 +33,8 @@ def _edge_in(e, du, dv):
     return (e > 0) | ((e == 0) & ((dv > 0) | ((dv == 0) & (du < 0))))
 
 
-def render_depth(verts_mm, tris, K, R, t, H, W, with_margin=False, with_counts=False):
-    """t in mm.  -> depth float32 [H,W] (metres, 0 = empty); with_margin=True also a bool [H,W] of pixel centres that lie within
-    1e-4 px of an edge of a drawn triangle (where a float rounding may flip coverage); with_counts=True (instead) an int [H,W]
-    of how many drawn triangles cover each centre."""
+def project(verts_mm, K, R, t):
+    """The rasteriser's vertex stage: t in mm -> (u, v, zc) per vertex, float64, the kernel's expressions in its order."""
     V = mesh_metres(verts_mm).astype(np.float64)
     R = np.asarray(R, np.float64).reshape(3, 3)
     t = pose_metres(t)
@@ -41,6 +47,14 @@ def render_depth(verts_mm, tris, K, R, t, H, W, with_margin=False, with_counts=F
     with np.errstate(divide="ignore", invalid="ignore"):
         u = fx * (xc / zc) + s * (yc / zc) + cx
         v = fy * (yc / zc) + cy
+    return u, v, zc
+
+
+def render_depth(verts_mm, tris, K, R, t, H, W, with_margin=False, with_counts=False):
+    """t in mm.  -> depth float32 [H,W] (metres, 0 = empty); with_margin=True also a bool [H,W] of pixel centres that lie within
+    1e-4 px of an edge of a drawn triangle (where a float rounding may flip coverage); with_counts=True (instead) an int [H,W]
+    of how many drawn triangles cover each centre."""
+    u, v, zc = project(verts_mm, K, R, t)
     zbuf = np.full((H, W), np.inf, np.float32)
     margin = np.zeros((H, W), bool)
     counts = np.zeros((H, W), np.int64)
@@ -93,8 +107,122 @@ def depth_score(depth_ref, depth_t, union_mask):
     inlier_mask = np.zeros(m.shape, bool)
     inlier_mask[m] = inl
     union = int(m.sum())
-    return {"inlier_count": int(inl.sum()), "union": union, "fcn": float(np.sum(np.maximum(0, 0.02 - diff) / 0.02)),
+    # np.fmax: a NaN sensor pixel adds 0 (the NaN rule, module docstring)
+    return {"inlier_count": int(inl.sum()), "union": union, "fcn": float(np.sum(np.fmax(0, 0.02 - diff) / 0.02)),
             "ratio": float(inl.sum()) / union if union else 0.0}, inlier_mask
+
+
+def score_ref32(depth_ref, depth_t, union_mask):
+    """icp3d.py:477-489 and fcn() at :314-315 as written, on float32 depth maps: numpy's own promotion (float32 throughout, the
+    Python float 0.02 taken as float32) and np.sum's pairwise float32 summation."""
+    depth_ref = np.asarray(depth_ref, np.float32)
+    depth_t = np.asarray(depth_t, np.float32)
+    union_mask = np.asarray(union_mask) != 0
+    inlier_mask = np.zeros(union_mask.shape, bool)
+    diff_depth = np.abs(depth_ref[union_mask] - depth_t[union_mask])
+    diff_mask = diff_depth < 0.02
+    inlier_mask[union_mask] = diff_mask
+    union = np.sum(union_mask)
+    fcn = np.sum(np.maximum(0, 0.02 - diff_depth) / 0.02)
+    return {"inlier_count": int(np.sum(diff_mask)), "union": int(union), "fcn": fcn,
+            "ratio": float(np.sum(diff_mask) / union) if union else 0.0}, inlier_mask
+
+
+def gl_pose(t_mm, R):
+    """render_obj (icp3d.py:40-50) as called by icp3d.py with tra_pred/1000: the 4 x 4 model pose in metres, quirk included."""
+    tra = np.asarray(t_mm, np.float64) / 1000
+    if tra[2] > 100:
+        tra = tra / 1000
+    pose = np.eye(4)
+    pose[:3, :3] = np.asarray(R, np.float64).reshape(3, 3)
+    pose[:3, 3] = tra
+    return pose
+
+
+def gl_projection(K, W, H, nc=CLIP_NEAR, fc=CLIP_FAR):
+    """Renderer.build_projection (renderer_xyz.py:186-201) with x0 = y0 = 0, as set_cam calls it; returns proj before its .T."""
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    q = -(fc + nc) / float(fc - nc)
+    qn = -2 * (fc * nc) / float(fc - nc)
+    proj = np.array([[2 * K[0, 0] / W, -2 * K[0, 1] / W, (-2 * K[0, 2] + W) / W, 0],
+                     [0, -2 * K[1, 1] / H, (-2 * K[1, 2] + H) / H, 0],
+                     [0, 0, q, qn],
+                     [0, 0, -1, 0]])
+    proj[1, :] *= -1.0
+    return proj
+
+
+def gl_window(verts_mm, K, R, t_mm, H, W):
+    """The reference's vertex transform as matrices: clip = proj @ yz_flip @ pose @ [X, 1] (draw_model uploads (yz_flip.pose).T
+    and proj.T, which a column-major mat4 reads back as these), divide by w, glViewport(0, 0, W, H) with depth range [0, 1], and
+    the read-back's row flip (finish(): [::-1]).  -> image-space (u, v) and the window depth d_w, float64 per vertex."""
+    V = mesh_metres(verts_mm).astype(np.float64)
+    yz_flip = np.diag([1.0, -1.0, -1.0, 1.0])
+    clip = gl_projection(K, W, H) @ yz_flip @ gl_pose(t_mm, R) @ np.vstack([V.T, np.ones(len(V))])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ndc = clip[:3] / clip[3]
+    x_w, y_w, d_w = (ndc[0] + 1) * W / 2, (ndc[1] + 1) * H / 2, (ndc[2] + 1) / 2
+    return x_w, H - y_w, d_w
+
+
+def gl_readback_depth(d_w, nc=CLIP_NEAR, fc=CLIP_FAR):
+    """finish() (renderer_xyz.py:140-153) on a float32 depth read-back: mult / (dep + addi), float32 as numpy evaluates it."""
+    dep = np.asarray(d_w, np.float32)
+    mult = (nc * fc) / (nc - fc)
+    addi = fc / (nc - fc)
+    return mult / (dep + addi)
+
+
+def raycast_depth(verts_mm, tris, K, R, t_mm, H, W, tol_px=1e-6, window=None):
+    """A second renderer, sharing nothing with render_depth but the input rules: every pixel centre's ray K^-1 (i + 0.5, j + 0.5, 1)
+    (skew included) is intersected with every triangle in camera space in float64 (Moller-Trumbore); the nearest hit of a triangle
+    facing the camera (geometric normal (b - a) x (c - a) against the view ray) wins.  A triangle with a vertex at z < 0.01 m is
+    rejected whole, hits beyond 10 m are dropped.  -> depth float64 [h, w] (0 = empty) and a margin mask of centres within tol_px
+    pixels (barycentric distance times the triangle's height over that edge on screen) of an edge of a drawn triangle, where
+    coverage is decided by the tie rule or by rounding.  window = (j0, j1, i0, i1) restricts both to rows j0:j1, columns i0:i1."""
+    j0, j1, i0, i1 = window if window is not None else (0, H, 0, W)
+    V = mesh_metres(verts_mm).astype(np.float64)
+    pose = gl_pose(t_mm, R)                      # the same t / 1000 and quirk
+    Vc = V @ pose[:3, :3].T + pose[:3, 3]
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    pu, pv = np.meshgrid(np.arange(i0, i1) + 0.5, np.arange(j0, j1) + 0.5)
+    rays = np.linalg.solve(K, np.stack([pu.ravel(), pv.ravel(), np.ones(pu.size)]))       # [3, N], z = 1
+    rays = rays / rays[2]
+    tris = np.asarray(tris, np.int64).reshape(-1, 3)
+    A, B, Cv = Vc[tris[:, 0]], Vc[tris[:, 1]], Vc[tris[:, 2]]
+    keep = np.all(Vc[tris][:, :, 2] >= CLIP_NEAR, axis=1)
+    nrm = np.cross(B - A, Cv - A)
+    keep &= np.einsum("ij,ij->i", nrm, A) < 0          # facing the camera (at the origin): its front is seen
+    A, B, Cv = A[keep], B[keep], Cv[keep]
+    # the triangle's screen image, for the margin only: vertex pixels and the height over each edge
+    P = [(K @ X.T) for X in (A, B, Cv)]
+    uv = [p[:2] / p[2] for p in P]
+    area2 = np.abs((uv[1][0] - uv[0][0]) * (uv[2][1] - uv[0][1]) - (uv[2][0] - uv[0][0]) * (uv[1][1] - uv[0][1]))
+    hts = [area2 / np.hypot(*(uv[(k + 2) % 3] - uv[(k + 1) % 3])) for k in range(3)]
+    depth = np.full(rays.shape[1], np.inf)
+    margin = np.zeros(rays.shape[1], bool)
+    d = rays.T[:, None, :]
+    for c0 in range(0, len(A), 64):
+        a, e1, e2 = A[c0:c0 + 64], B[c0:c0 + 64] - A[c0:c0 + 64], Cv[c0:c0 + 64] - A[c0:c0 + 64]
+        pvec = np.cross(d, e2[None])
+        det = np.einsum("nmk,mk->nm", pvec, e1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / det
+            tvec = -a
+            b1 = np.einsum("nmk,mk->nm", pvec, tvec) * inv
+            qvec = np.cross(tvec, e1)                       # [m, 3]
+            b2 = (d[:, 0, :] @ qvec.T) * inv
+            s = (e2 * qvec).sum(1)[None] * inv             # ray parameter = camera z (ray z = 1)
+        b0 = 1.0 - b1 - b2
+        hit = (b0 >= 0) & (b1 >= 0) & (b2 >= 0) & (s >= CLIP_NEAR) & (s <= CLIP_FAR)
+        depth = np.minimum(depth, np.where(hit, s, np.inf).min(axis=1, initial=np.inf))
+        # screen barycentrics lam_k = b_k z_k / z; times the height over edge k: signed pixel distance to that edge's line
+        zs = [a[:, 2], B[c0:c0 + 64, 2], Cv[c0:c0 + 64, 2]]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dist = np.min([bk * zk[None] / s * h[c0:c0 + 64][None] for bk, zk, h in zip((b0, b1, b2), zs, hts)], axis=0)
+        margin |= np.any((np.abs(dist) <= tol_px) & (s > 0), axis=1)
+    depth = np.where(np.isinf(depth), 0.0, depth)
+    return depth.reshape(pu.shape), margin.reshape(pu.shape)
 
 
 def box_mesh(lo, hi, n=8):
@@ -163,3 +291,21 @@ def pixel_grid_mesh():
 
 
 GRID_K = np.array([[64.0, 0.0, 320.5], [0.0, 64.0, 240.5], [0.0, 0.0, 1.0]])
+
+
+# Cameras at the sizes the depth path runs at (LINEMOD / YCB 640 x 480, T-LESS 720 x 540, ITODD 1280 x 960, an odd size), with
+# skew of both signs, fx != fy and principal points far from the image centre.  (K, H, W).
+CAMERAS = [
+    (np.array([[572.4114, 3.7, 180.0], [0.0, 573.57043, 330.0], [0.0, 0.0, 1.0]]), 480, 640),
+    (np.array([[1075.65, -2.5, 500.0], [0.0, 1073.90, 120.0], [0.0, 0.0, 1.0]]), 540, 720),
+    (np.array([[2990.0, 6.0, 640.5], [0.0, 2985.0, 700.0], [0.0, 0.0, 1.0]]), 960, 1280),
+    (np.array([[60.0, -1.5, 12.0], [0.0, 45.0, 26.0], [0.0, 0.0, 1.0]]), 37, 53),
+]
+
+
+def random_pose(rs, K, H, W, zlo=0.35, zhi=1.2):
+    """A random rotation and a t (mm) that puts the origin near a random point of the image at depth zlo..zhi m."""
+    R = rot(0, rs.uniform(-180, 180)) @ rot(1, rs.uniform(-180, 180)) @ rot(2, rs.uniform(-180, 180))
+    z = rs.uniform(zlo, zhi)
+    p = np.linalg.solve(np.asarray(K, np.float64), [rs.uniform(0.2, 0.8) * W, rs.uniform(0.2, 0.8) * H, 1.0])
+    return R, p / p[2] * z * 1000.0
