@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define P2P_ABI_VERSION 10
+#define P2P_ABI_VERSION 11
 
 /* The library is built with -fvisibility=hidden: the entry points declared here (P2P_API) are its ONLY dynamic symbols
  * (tests/test_host_cpu.py holds `nm -D` to exactly this list). */
@@ -57,7 +57,7 @@ typedef struct {
 P2P_API int p2p_abi_version(void);
 /* Binding self-checks: sizeof() of the public structs as this build of the library sees them
  * (which: 0 p2p_tensor, 1 p2p_image, 2 p2p_object, 3 p2p_detection, 4 p2p_pose, 5 p2p_est_pose_opts,
- * 6 p2p_kernel_stats, 7 p2p_refine_job, 8 p2p_depth_score; -1 otherwise), and the hash of the sources the library was built from
+ * 6 p2p_kernel_stats, 7 p2p_refine_job, 8 p2p_depth_score, 9 p2p_icp_input; -1 otherwise), and the hash of the sources the library was built from
  * (pix2pose_amd/build.py) -- a foreign-language binding compares both with its own declarations / tree
  * before the first call, so that a stale .so is an error and not a silent struct mismatch. */
 P2P_API int p2p_abi_sizeof(int which);
@@ -426,7 +426,8 @@ P2P_API void p2p_mesh_destroy(p2p_mesh* mesh);
  * library hands t/1000 to the rasteriser like icp3d.py passes tra_pred/1000 to render_obj(), and keeps render_obj's unit quirk on
  * that value (:46: tra[2] > 100 m is taken as mm and divided by 1000 once more).  img_idx indexes the depth images of
  * p2p_depth_score_batch (ignored by p2p_render_depth_batch); union_mask is a host u8 [height*width] (nonzero = in the union mask,
- * p2p_depth_score_batch only).  This is the job record the depth refinement entry point (ICP, not built yet) is to take as well. */
+ * p2p_depth_score_batch and p2p_icp_inputs_batch).  This is the job record the depth refinement entry point (ICP, not built yet) is to
+ * take as well. */
 typedef struct {
     int img_idx;
     int mesh_idx;
@@ -458,6 +459,50 @@ typedef struct {
 P2P_API int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
                                   int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_depth_score* out,
                                   unsigned char* inlier_masks);
+
+/* ------------------------------------------------------------------------------------------
+ * Depth back-projection, normals and the ICP point sets (csrc/normals.hip).  A point is 6 float32
+ * [x y z nx ny nz], xyz in the depth's unit (metres).  Normals follow get_normal(refine=True) with cv2.inpaint replaced by the
+ * onion-peel fill of DESIGN.md 8 (outputs at pixels with d > 0 do not depend on the fill's depth); pixel offsets are the reference's
+ * int16 (u - cx), (v - cy), truncated toward zero, and the skew camK[1] is not used.  Image sizes from 3 x 3 to 16384 x 16384
+ * (at most 2^26 pixels), cameras with finite nonzero fx, fy and |cx|, |cy| < 16384; anything else is P2P_ERR_INVALID_ARG.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Scene points of whole frames (replaces getXYZ + get_normal(refine=True) at icp3d.py:372-374): depth_images[i] host float32
+ * [height][width] in metres, camK [n_images][9] (row-major 3 x 3), points host float32 [n_images][height][width][6]. */
+P2P_API int p2p_depth_points_batch(p2p_ctx* ctx, const float* const* depth_images, int n_images, const double* camK, int height,
+                                   int width, float* points);
+
+/* Status of an ICP input record.  Both nonzero values are the reference's `return tf, -1` (icp_refinement :70-73). */
+enum {
+    P2P_ICP_OK = 0,
+    P2P_ICP_SMALL_BBOX = -1,      /* bbox of init_mask: rmax - rmin < 5 or cmax - cmin < 5 (also an empty init_mask) */
+    P2P_ICP_FEW_POINTS = -2       /* fewer than 10 init_mask pixels in the whole image */
+};
+
+/* One job's ICP inputs.  Offsets and counts are in points, into the packed buffers of p2p_icp_inputs_batch.  bbox is
+ * get_bbox_from_mask(init_mask) = [rmin, cmin, rmax, cmax], max inclusive (zeros for an empty mask).  t_init: job.t after the
+ * 300 / 5000 mm replacement (t := centroid_tgt * 1000), the pose that is rendered; t_adjusted = t_init + (centroid_tgt - centroid_src)
+ * * 1000 (mm).  Centroids are float64 means of the stored float32 xyz (before the shift of the source points); an empty set gives NaN.
+ * When status != 0: n_src = 0, centroid_src = 0 and t_adjusted = t_init. */
+typedef struct {
+    int status;
+    int bbox[4];
+    int64_t src_offset, n_src, tgt_offset, n_tgt;
+    double t_init[3], t_adjusted[3], centroid_src[3], centroid_tgt[3];
+} p2p_icp_input;
+
+/* The point sets icp_refinement hands to cv2.ppf_match_3d_ICP (icp3d.py:464 and icp_refinement :58-85, up to registerModelToScene):
+ *   target: points_tgt[union_mask], the scene points of depth_images[job.img_idx] (computed once per image and camera in a call);
+ *   source: at t_init, the render's init_mask = (depth > 0) & union_mask, its bbox and gates, then the points with normals of the
+ *           rendered depth over [rmin, rmax) x [cmin, cmax) where init_mask is set, xyz shifted by centroid_tgt - centroid_src.
+ * job.union_mask is used as given (the caller ANDs in depth_valid, icp3d.py:455-456).  Points are in numpy's boolean-index (row-major)
+ * order, packed in job order into src_points [src_capacity][6] and tgt_points [tgt_capacity][6] (host float32).  A null buffer is
+ * not written (records only).  A buffer too small for its points gives P2P_ERR_CAPACITY with every record filled in and no points
+ * written, so the caller can size the buffers and call again.  Bit-identical for a job alone or in a batch. */
+P2P_API int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                                 int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out,
+                                 float* src_points, int64_t src_capacity, float* tgt_points, int64_t tgt_capacity);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("P2P_LIB", os.path.join(_HERE, "libp2p_mi355.so"))     # P2P_LIB: development override
 
 P2P_OK = 0
-ABI_VERSION = 10           # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
+ABI_VERSION = 11           # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
 MAX_RANSAC_ITERATIONS = 128
 BACKBONE = {"paper": 0, "resnet50": 1}
 PRECISION = {"f32": 0, "f16x3": 1, "auto": 2}     # p2p_precision; "auto" = split-f16 with an fp32 twin it falls back to on a range event
@@ -117,6 +117,16 @@ class DepthScore(C.Structure):
     _fields_ = [("inlier_count", C.c_int64), ("union_count", C.c_int64), ("fcn", C.c_double), ("ratio", C.c_double)]
 
 
+class IcpInput(C.Structure):
+    _fields_ = [("status", C.c_int), ("bbox", C.c_int * 4), ("src_offset", C.c_int64), ("n_src", C.c_int64),
+                ("tgt_offset", C.c_int64), ("n_tgt", C.c_int64), ("t_init", C.c_double * 3), ("t_adjusted", C.c_double * 3),
+                ("centroid_src", C.c_double * 3), ("centroid_tgt", C.c_double * 3)]
+
+
+ERR_CAPACITY = -4
+ICP_OK, ICP_SMALL_BBOX, ICP_FEW_POINTS = 0, -1, -2     # p2p_icp_input.status; both nonzero values are the reference's -1
+
+
 _lib = None
 
 
@@ -180,7 +190,8 @@ def _stale_reason_of(L):
             return "built from other sources (build id %s, tree %s)" % (got, want)
     L.p2p_abi_sizeof.restype = C.c_int
     L.p2p_abi_sizeof.argtypes = [C.c_int]
-    for which, typ in enumerate((Tensor, Image, Object, Detection, Pose, EstPoseOpts, KernelStats, RefineJob, DepthScore)):
+    for which, typ in enumerate((Tensor, Image, Object, Detection, Pose, EstPoseOpts, KernelStats, RefineJob, DepthScore,
+                                   IcpInput)):
         if L.p2p_abi_sizeof(which) != C.sizeof(typ):
             return "sizeof(%s) = %d in the library, %d in the binding" % (typ.__name__, L.p2p_abi_sizeof(which), C.sizeof(typ))
     return None
@@ -254,6 +265,9 @@ def lib():
     L.p2p_render_depth_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci, vp]
     L.p2p_depth_score_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
                                         C.POINTER(DepthScore), vp]
+    L.p2p_depth_points_batch.argtypes = [vp, C.POINTER(vp), ci, dp, ci, ci, vp]
+    L.p2p_icp_inputs_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
+                                       C.POINTER(IcpInput), vp, C.c_int64, vp, C.c_int64]
     _lib = L
     return L
 

@@ -199,6 +199,8 @@ __global__ void __launch_bounds__(SCORE_THREADS) depth_score_kernel(const float*
     }
 }
 
+}  // namespace
+
 int check_jobs(const char* who, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W,
                int n_images)
 {
@@ -268,7 +270,6 @@ int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* job
     return P2P_OK;
 }
 
-}  // namespace
 }  // namespace p2p
 
 using namespace p2p;

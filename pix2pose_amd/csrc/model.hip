@@ -1704,6 +1704,7 @@ int p2p_abi_sizeof(int which)
     case 6: return (int)sizeof(p2p_kernel_stats);
     case 7: return (int)sizeof(p2p_refine_job);
     case 8: return (int)sizeof(p2p_depth_score);
+    case 9: return (int)sizeof(p2p_icp_input);
     default: return -1;
     }
 }

@@ -204,4 +204,10 @@ struct Comm;
 int comm_world(const Comm& C);
 int comm_gather(Ctx& X, Comm& C, Slot* s, bool range_event, hipStream_t ts, int n_max, p2p_pose* gathered);
 
+// Depth path (depth.hip), shared with the ICP inputs (normals.hip): argument checks of a job list (n_images < 0: img_idx and
+// union_mask unchecked), and the z-buffer of every job into zbuf [n_jobs][H][W] (device, float bits, 0 where nothing is drawn).
+int check_jobs(const char* who, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W,
+               int n_images);
+int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, unsigned* zbuf, DevBuf& djobs);
+
 }  // namespace p2p

@@ -520,3 +520,63 @@ def depth_score_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = F
     out = [{"inlier_count": int(r.inlier_count), "union": int(r.union_count), "fcn": float(r.fcn), "ratio": float(r.ratio)}
            for r in res[:len(jobs)]]
     return (out, masks.astype(bool)) if inlier_masks else out
+
+
+def depth_points_batch(ctx: Context, depths, camKs):
+    """Scene points of whole frames (p2p_depth_points_batch; replaces getXYZ + get_normal(refine=True), icp3d.py:372-374): depths
+    float32 [H, W] in metres, camKs [3, 3] each -> float32 [n, H, W, 6] = x y z nx ny nz."""
+    depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+    if len(depths) != len(camKs):
+        raise ValueError("one camera per depth image")
+    if not depths:
+        raise ValueError("depth_points_batch needs at least one depth image")
+    H, W = depths[0].shape
+    if any(d.shape != (H, W) for d in depths):
+        raise ValueError("all depth images must have the same size")
+    K = np.ascontiguousarray(np.asarray(camKs, np.float64).reshape(len(depths), 9))
+    dp = (C.c_void_p * len(depths))(*[d.ctypes.data for d in depths])
+    out = np.empty((len(depths), H, W, 6), np.float32)
+    _lib.check(_lib.lib().p2p_depth_points_batch(ctx.handle, dp, len(depths), K.ctypes.data_as(C.POINTER(C.c_double)), H, W,
+                                                 out.ctypes.data), "p2p_depth_points_batch")
+    return out
+
+
+def icp_inputs_batch(ctx: Context, meshes, depths, jobs):
+    """The point sets of the ICP refinement (p2p_icp_inputs_batch; icp3d.py:464 and icp_refinement :58-85 up to registerModelToScene).
+    depths: float32 [H, W] metres; jobs as in _depth_jobs, each with an 'image' and a 'union_mask' (depth_valid already ANDed in).
+    Returns one dict per job: status (0, or _lib.ICP_SMALL_BBOX / ICP_FEW_POINTS, both the reference's -1), bbox, t_init, t_adjusted,
+    centroid_src, centroid_tgt, and src / tgt float32 [k, 6] (x y z nx ny nz)."""
+    depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+    if not depths:
+        raise ValueError("icp_inputs_batch needs at least one depth image")
+    H, W = depths[0].shape
+    if any(d.shape != (H, W) for d in depths):
+        raise ValueError("all depth images must have the same size")
+    for j in jobs:
+        if j.get("union_mask") is None or np.shape(j["union_mask"]) != (H, W):
+            raise ValueError("every job needs a union_mask of the depth images' size %r" % ((H, W),))
+    keep = []
+    arr = _depth_jobs(jobs, keep)
+    mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+    dp = (C.c_void_p * len(depths))(*[d.ctypes.data for d in depths])
+    res = (_lib.IcpInput * max(1, len(jobs)))()
+    # init_mask is a subset of union_mask, so the union sizes bound both point sets; the retry covers a binding that guesses smaller
+    n_tgt = sum(int(m.sum()) for m in keep)
+    cap_src, cap_tgt = n_tgt, n_tgt
+    while True:
+        src = np.empty((max(cap_src, 1), 6), np.float32)
+        tgt = np.empty((max(cap_tgt, 1), 6), np.float32)
+        rc = _lib.lib().p2p_icp_inputs_batch(ctx.handle, mh, len(meshes), dp, len(depths), arr, len(jobs), H, W, res,
+                                             src.ctypes.data, cap_src, tgt.ctypes.data, cap_tgt)
+        if rc != _lib.ERR_CAPACITY:
+            break
+        recs = res[:len(jobs)]
+        cap_src = max(cap_src, sum(int(r.n_src) for r in recs))
+        cap_tgt = max(cap_tgt, sum(int(r.n_tgt) for r in recs))
+    _lib.check(rc, "p2p_icp_inputs_batch")
+    out = []
+    for r in res[:len(jobs)]:
+        out.append({"status": int(r.status), "bbox": list(r.bbox), "t_init": np.array(r.t_init[:]), "t_adjusted": np.array(r.t_adjusted[:]),
+                    "centroid_src": np.array(r.centroid_src[:]), "centroid_tgt": np.array(r.centroid_tgt[:]),
+                    "src": src[r.src_offset:r.src_offset + r.n_src].copy(), "tgt": tgt[r.tgt_offset:r.tgt_offset + r.n_tgt].copy()})
+    return out
