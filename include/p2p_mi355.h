@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define P2P_ABI_VERSION 11
+#define P2P_ABI_VERSION 12
 
 /* The library is built with -fvisibility=hidden: the entry points declared here (P2P_API) are its ONLY dynamic symbols
  * (tests/test_host_cpu.py holds `nm -D` to exactly this list). */
@@ -57,7 +57,8 @@ typedef struct {
 P2P_API int p2p_abi_version(void);
 /* Binding self-checks: sizeof() of the public structs as this build of the library sees them
  * (which: 0 p2p_tensor, 1 p2p_image, 2 p2p_object, 3 p2p_detection, 4 p2p_pose, 5 p2p_est_pose_opts,
- * 6 p2p_kernel_stats, 7 p2p_refine_job, 8 p2p_depth_score, 9 p2p_icp_input; -1 otherwise), and the hash of the sources the library was built from
+ * 6 p2p_kernel_stats, 7 p2p_refine_job, 8 p2p_depth_score, 9 p2p_icp_input, 10 p2p_icp_params, 11 p2p_icp_result,
+ * 12 p2p_refine_result; -1 otherwise), and the hash of the sources the library was built from
  * (pix2pose_amd/build.py) -- a foreign-language binding compares both with its own declarations / tree
  * before the first call, so that a stale .so is an error and not a silent struct mismatch. */
 P2P_API int p2p_abi_sizeof(int which);
@@ -426,8 +427,8 @@ P2P_API void p2p_mesh_destroy(p2p_mesh* mesh);
  * library hands t/1000 to the rasteriser like icp3d.py passes tra_pred/1000 to render_obj(), and keeps render_obj's unit quirk on
  * that value (:46: tra[2] > 100 m is taken as mm and divided by 1000 once more).  img_idx indexes the depth images of
  * p2p_depth_score_batch (ignored by p2p_render_depth_batch); union_mask is a host u8 [height*width] (nonzero = in the union mask,
- * p2p_depth_score_batch and p2p_icp_inputs_batch).  This is the job record the depth refinement entry point (ICP, not built yet) is to
- * take as well. */
+ * p2p_depth_score_batch, p2p_icp_inputs_batch and p2p_refine_depth_batch).  It is also the job record of the depth refinement entry
+ * point p2p_refine_depth_batch. */
 typedef struct {
     int img_idx;
     int mesh_idx;
@@ -477,7 +478,10 @@ P2P_API int p2p_depth_points_batch(p2p_ctx* ctx, const float* const* depth_image
 enum {
     P2P_ICP_OK = 0,
     P2P_ICP_SMALL_BBOX = -1,      /* bbox of init_mask: rmax - rmin < 5 or cmax - cmin < 5 (also an empty init_mask) */
-    P2P_ICP_FEW_POINTS = -2       /* fewer than 10 init_mask pixels in the whole image */
+    P2P_ICP_FEW_POINTS = -2,      /* fewer than 10 init_mask pixels in the whole image */
+    P2P_ICP_NONFINITE = -3        /* p2p_icp_batch / p2p_refine_depth_batch only: a source or target xyz is not finite (a NaN sensor
+                                   * pixel inside the union mask), or the normalisation scale is not (every point at the mean);
+                                   * p2p_icp_inputs_batch never returns it */
 };
 
 /* One job's ICP inputs.  Offsets and counts are in points, into the packed buffers of p2p_icp_inputs_batch.  bbox is
@@ -503,6 +507,58 @@ typedef struct {
 P2P_API int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
                                  int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out,
                                  float* src_points, int64_t src_capacity, float* tgt_points, int64_t tgt_capacity);
+
+/* ------------------------------------------------------------------------------------------
+ * Point-to-plane ICP and the depth refinement entry point (csrc/icp.hip).  The ICP is a named, deterministic
+ * restatement of cv::ppf_match_3d::ICP::registerModelToScene (opencv-contrib 3.4.2, the reference's pin): its rules are written down
+ * in DESIGN.md 8.2 and held by tests/icp_ref.py; it is not pinned to the OpenCV binary.  A job's result is bit-identical alone or in a
+ * batch.
+ * ---------------------------------------------------------------------------------------- */
+#define P2P_ICP_MAX_LEVELS 8
+/* cv2.ppf_match_3d_ICP(iterations, tolerence, rejectionScale, numLevels); a null pointer means the reference's 100, 0.005, 2.5, 2.
+ * num_levels outside 1..8, max_iterations < 1, or a non-finite tolerance / rejection_scale is P2P_ERR_INVALID_ARG.  rejection_scale
+ * <= 0 turns the robust rejection off (every pair is kept), as in OpenCV. */
+typedef struct {
+    int max_iterations;
+    float tolerance;
+    float rejection_scale;
+    int num_levels;
+} p2p_icp_params;
+
+typedef struct {
+    int status;                              /* 0, P2P_ICP_SMALL_BBOX, P2P_ICP_FEW_POINTS (passed through) or P2P_ICP_NONFINITE */
+    int iterations[P2P_ICP_MAX_LEVELS];      /* iterations run per pyramid level, index = level (0 = finest) */
+    int pairs[P2P_ICP_MAX_LEVELS];           /* selInd of the level's last iteration (0: no iteration) */
+    double fval_min[P2P_ICP_MAX_LEVELS];     /* least residual of the level (9999999999 when it ran no iteration); diagnostic */
+    double scale, mean_avg[3];               /* the normalisation: xyz -> (xyz - mean_avg) * scale */
+    double pose[16];                         /* row-major 4 x 4, metres: registerModelToScene's pose (identity when status != 0) */
+} p2p_icp_result;
+
+/* ICP of packed point sets as p2p_icp_inputs_batch returns them: job k registers src_points[inputs[k].src_offset ..][6] (n_src rows)
+ * to tgt_points[inputs[k].tgt_offset ..][6] (n_tgt rows), host float32.  Records with status != 0 are passed through with an
+ * identity pose.  A job of status 0 with no target point, or whose source is too small for the pyramid (rint(n_src / 2^(levels-1))
+ * = 0), is P2P_ERR_INVALID_ARG. */
+P2P_API int p2p_icp_batch(p2p_ctx* ctx, const p2p_icp_input* inputs, int n_jobs, const float* src_points, const float* tgt_points,
+                          const p2p_icp_params* params, p2p_icp_result* out);
+
+/* The depth refinement of one frame's detections (icp3d.py:455-491): per job, the ICP inputs of p2p_icp_inputs_batch, the ICP above
+ * on them without leaving the device, the refined pose tf = icp.pose * [job.R | input.t_adjusted / 1000] (R = tf[:3,:3], t =
+ * tf[:3,3] * 1000 mm), and the depth score of p2p_depth_score_batch at (R, t) against the same image and union mask.  A job whose
+ * status is not 0 keeps job.R / job.t, an identity icp.pose and a zero score (its inlier mask is all 0).  inlier_masks as in
+ * p2p_depth_score_batch (may be null).  The parameter checks of p2p_icp_batch hold per call: a status-0 job whose source is too small
+ * for params->num_levels (rint(n_src / 2^(levels-1)) = 0) fails the whole call with P2P_ERR_INVALID_ARG, and n_src is only known
+ * inside the call.  With at most 5 levels this cannot happen (a status-0 job has at least 10 source points). */
+typedef struct {
+    p2p_icp_input input;
+    p2p_icp_result icp;
+    double R[9];
+    double t[3];
+    p2p_depth_score score;
+} p2p_refine_result;
+
+P2P_API int p2p_refine_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                                   int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width,
+                                   const p2p_icp_params* params, p2p_refine_result* out, unsigned char* inlier_masks);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("P2P_LIB", os.path.join(_HERE, "libp2p_mi355.so"))     # P2P_LIB: development override
 
 P2P_OK = 0
-ABI_VERSION = 11           # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
+ABI_VERSION = 12           # P2P_ABI_VERSION of include/p2p_mi355.h these ctypes declarations follow
 MAX_RANSAC_ITERATIONS = 128
 BACKBONE = {"paper": 0, "resnet50": 1}
 PRECISION = {"f32": 0, "f16x3": 1, "auto": 2}     # p2p_precision; "auto" = split-f16 with an fp32 twin it falls back to on a range event
@@ -123,8 +123,26 @@ class IcpInput(C.Structure):
                 ("centroid_src", C.c_double * 3), ("centroid_tgt", C.c_double * 3)]
 
 
+ICP_MAX_LEVELS = 8    # P2P_ICP_MAX_LEVELS
+
+
+class IcpParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("tolerance", C.c_float), ("rejection_scale", C.c_float), ("num_levels", C.c_int)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int * ICP_MAX_LEVELS), ("pairs", C.c_int * ICP_MAX_LEVELS),
+                ("fval_min", C.c_double * ICP_MAX_LEVELS), ("scale", C.c_double), ("mean_avg", C.c_double * 3),
+                ("pose", C.c_double * 16)]
+
+
+class RefineResult(C.Structure):
+    _fields_ = [("input", IcpInput), ("icp", IcpResult), ("R", C.c_double * 9), ("t", C.c_double * 3), ("score", DepthScore)]
+
+
 ERR_CAPACITY = -4
 ICP_OK, ICP_SMALL_BBOX, ICP_FEW_POINTS = 0, -1, -2     # p2p_icp_input.status; both nonzero values are the reference's -1
+ICP_NONFINITE = -3                                     # p2p_icp_result.status: a non-finite source or target xyz
 
 
 _lib = None
@@ -191,7 +209,7 @@ def _stale_reason_of(L):
     L.p2p_abi_sizeof.restype = C.c_int
     L.p2p_abi_sizeof.argtypes = [C.c_int]
     for which, typ in enumerate((Tensor, Image, Object, Detection, Pose, EstPoseOpts, KernelStats, RefineJob, DepthScore,
-                                   IcpInput)):
+                                   IcpInput, IcpParams, IcpResult, RefineResult)):
         if L.p2p_abi_sizeof(which) != C.sizeof(typ):
             return "sizeof(%s) = %d in the library, %d in the binding" % (typ.__name__, L.p2p_abi_sizeof(which), C.sizeof(typ))
     return None
@@ -268,6 +286,9 @@ def lib():
     L.p2p_depth_points_batch.argtypes = [vp, C.POINTER(vp), ci, dp, ci, ci, vp]
     L.p2p_icp_inputs_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
                                        C.POINTER(IcpInput), vp, C.c_int64, vp, C.c_int64]
+    L.p2p_icp_batch.argtypes = [vp, C.POINTER(IcpInput), ci, vp, vp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    L.p2p_refine_depth_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
+                                         C.POINTER(IcpParams), C.POINTER(RefineResult), vp]
     _lib = L
     return L
 

@@ -270,6 +270,17 @@ int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* job
     return P2P_OK;
 }
 
+int score_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, const float* images,
+               const int* img_of, const unsigned char* masks, unsigned char* inl, p2p_depth_score* out, DevBuf& dz, DevBuf& djobs)
+{
+    const size_t HW = (size_t)H * W;
+    int rc;
+    if ((rc = dz.reserve(n_jobs * HW * 4)) || (rc = render_into(X, meshes, jobs, n_jobs, H, W, dz.as<unsigned>(), djobs))) return rc;
+    depth_score_kernel<<<n_jobs, SCORE_THREADS, 0, X.stream>>>(dz.as<float>(), images, img_of, masks, (int)HW, inl, out);
+    DEPTH_TRY(hipGetLastError());
+    return P2P_OK;
+}
+
 }  // namespace p2p
 
 using namespace p2p;
@@ -367,7 +378,7 @@ int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mes
     const size_t HW = (size_t)height * width;
     DevBuf dz, dj, dimg, dmask, dof, dinl, dout;
     auto cleanup = [&]() { dz.release(); dj.release(); dimg.release(); dmask.release(); dof.release(); dinl.release(); dout.release(); };
-    if ((rc = dz.reserve(n_jobs * HW * 4)) || (rc = dimg.reserve(n_images * HW * 4)) || (rc = dmask.reserve(n_jobs * HW)) ||
+    if ((rc = dimg.reserve(n_images * HW * 4)) || (rc = dmask.reserve(n_jobs * HW)) ||
         (rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
         (inlier_masks && (rc = dinl.reserve(n_jobs * HW)))) {
         cleanup();
@@ -386,15 +397,12 @@ int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mes
         cleanup();
         return P2P_ERR_HIP;
     }
-    if ((rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) {
+    if ((rc = score_into(*c, meshes, jobs, n_jobs, height, width, dimg.as<float>(), dof.as<int>(), dmask.as<unsigned char>(),
+                         inlier_masks ? dinl.as<unsigned char>() : nullptr, dout.as<p2p_depth_score>(), dz, dj))) {
         cleanup();
         return rc;
     }
-    depth_score_kernel<<<n_jobs, SCORE_THREADS, 0, st>>>(dz.as<float>(), dimg.as<float>(), dof.as<int>(), dmask.as<unsigned char>(),
-                                                         (int)HW, inlier_masks ? dinl.as<unsigned char>() : nullptr,
-                                                         dout.as<p2p_depth_score>());
-    if ((e = hipGetLastError()) != hipSuccess ||
-        (e = hipMemcpyAsync(out, dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(out, dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st)) != hipSuccess ||
         (inlier_masks && (e = hipMemcpyAsync(inlier_masks, dinl.p, n_jobs * HW, hipMemcpyDeviceToHost, st)) != hipSuccess) ||
         (e = hipStreamSynchronize(st)) != hipSuccess) {
         set_error("p2p_depth_score_batch: %s", hipGetErrorString(e));

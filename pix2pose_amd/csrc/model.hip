@@ -1705,6 +1705,9 @@ int p2p_abi_sizeof(int which)
     case 7: return (int)sizeof(p2p_refine_job);
     case 8: return (int)sizeof(p2p_depth_score);
     case 9: return (int)sizeof(p2p_icp_input);
+    case 10: return (int)sizeof(p2p_icp_params);
+    case 11: return (int)sizeof(p2p_icp_result);
+    case 12: return (int)sizeof(p2p_refine_result);
     default: return -1;
     }
 }

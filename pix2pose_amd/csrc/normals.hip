@@ -514,13 +514,21 @@ int p2p_depth_points_batch(p2p_ctx* ctx, const float* const* depth_images, int n
     return P2P_OK;
 }
 
-int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images, int n_images,
-                         const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, float* src_points,
-                         int64_t src_capacity, float* tgt_points, int64_t tgt_capacity)
+}  // extern "C"
+
+namespace p2p {
+
+void IcpInputsStage::release()
 {
-    const char* who = "p2p_icp_inputs_batch";
-    if (!ctx || n_jobs < 0 || n_jobs > 65535 || n_images < 0 || (n_jobs > 0 && (!meshes || !jobs || !out || !depth_images)) ||
-        src_capacity < 0 || tgt_capacity < 0) {
+    for (DevBuf* b : {&dimg, &dumask, &dscene, &dwork, &ditems, &dcmp, &drow, &dcmp2, &drow2, &dtgt, &dsrc, &dz, &dj, &dbox, &dctgt,
+                      &dcsrc, &djob_of, &dwork2, &ditems2})
+        b->release();
+}
+
+int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S)
+{
+    if (!ctx || n_jobs < 0 || n_jobs > 65535 || n_images < 0 || (n_jobs > 0 && (!meshes || !jobs || !out || !depth_images))) {
         set_error("%s: bad arguments", who);
         return P2P_ERR_INVALID_ARG;
     }
@@ -542,12 +550,10 @@ int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mesh
     const bool whole = dev_env("P2P_NORMALS_WHOLE") != nullptr;     // development twin: jobs' fill and Gaussian over the whole frame
 
     // (every buffer has one use: DevBuf::reserve frees, so a buffer read by queued work is never grown)
-    DevBuf dimg, dumask, dscene, dwork, ditems, dcmp, drow, dcmp2, drow2, dtgt, dsrc, dz, dj, dbox, dctgt, dcsrc, djob_of, dwork2, ditems2;
-    auto cleanup = [&]() {
-        for (DevBuf* b : {&dimg, &dumask, &dscene, &dwork, &ditems, &dcmp, &drow, &dcmp2, &drow2, &dtgt, &dsrc, &dz, &dj, &dbox, &dctgt,
-                          &dcsrc, &djob_of, &dwork2, &ditems2})
-            b->release();
-    };
+    DevBuf &dimg = S.dimg, &dumask = S.dumask, &dscene = S.dscene, &dwork = S.dwork, &ditems = S.ditems, &dcmp = S.dcmp, &drow = S.drow,
+           &dcmp2 = S.dcmp2, &drow2 = S.drow2, &dtgt = S.dtgt, &dsrc = S.dsrc, &dz = S.dz, &dj = S.dj, &dbox = S.dbox, &dctgt = S.dctgt,
+           &dcsrc = S.dcsrc, &djob_of = S.djob_of, &dwork2 = S.dwork2, &ditems2 = S.ditems2;
+    auto cleanup = [&]() { S.release(); };
 #define NRM_STEP(expr)              \
     do {                            \
         if ((rc = (expr))) {        \
@@ -703,18 +709,50 @@ int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mesh
         }
     }
 
-    // 6. the point buffers, if they are given and large enough
-    if ((src_points && tot_src > src_capacity) || (tgt_points && tot_tgt > tgt_capacity)) {
-        set_error("%s: %lld source / %lld target points, capacities %lld / %lld", who, (long long)tot_src, (long long)tot_tgt,
+    S.slot_of = slot_of;
+    S.tot_src = tot_src;
+    S.tot_tgt = tot_tgt;
+#undef NRM_STEP
+    return P2P_OK;
+}
+
+}  // namespace p2p
+
+extern "C" {
+
+int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images, int n_images,
+                         const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, float* src_points,
+                         int64_t src_capacity, float* tgt_points, int64_t tgt_capacity)
+{
+    const char* who = "p2p_icp_inputs_batch";
+    if (src_capacity < 0 || tgt_capacity < 0) {
+        set_error("%s: bad arguments", who);
+        return P2P_ERR_INVALID_ARG;
+    }
+    IcpInputsStage S;
+    int rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, out, S);
+    if (rc || n_jobs == 0) {
+        S.release();
+        return rc;
+    }
+    hipStream_t st = reinterpret_cast<Ctx*>(ctx)->stream;
+
+    // the point buffers, if they are given and large enough
+    if ((src_points && S.tot_src > src_capacity) || (tgt_points && S.tot_tgt > tgt_capacity)) {
+        set_error("%s: %lld source / %lld target points, capacities %lld / %lld", who, (long long)S.tot_src, (long long)S.tot_tgt,
                   (long long)src_capacity, (long long)tgt_capacity);
-        cleanup();
+        S.release();
         return P2P_ERR_CAPACITY;
     }
-    if (src_points && tot_src > 0) NRM_STEP(hip(hipMemcpyAsync(src_points, dsrc.p, tot_src * 24, hipMemcpyDeviceToHost, st)));
-    if (tgt_points && tot_tgt > 0) NRM_STEP(hip(hipMemcpyAsync(tgt_points, dtgt.p, tot_tgt * 24, hipMemcpyDeviceToHost, st)));
-    NRM_STEP(hip(hipStreamSynchronize(st)));
-#undef NRM_STEP
-    cleanup();
+    hipError_t e = hipSuccess;
+    if (src_points && S.tot_src > 0) e = hipMemcpyAsync(src_points, S.dsrc.p, S.tot_src * 24, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && tgt_points && S.tot_tgt > 0) e = hipMemcpyAsync(tgt_points, S.dtgt.p, S.tot_tgt * 24, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    S.release();
+    if (e != hipSuccess) {
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return P2P_ERR_HIP;
+    }
     return P2P_OK;
 }
 

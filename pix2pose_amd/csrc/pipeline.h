@@ -209,5 +209,21 @@ int comm_gather(Ctx& X, Comm& C, Slot* s, bool range_event, hipStream_t ts, int 
 int check_jobs(const char* who, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W,
                int n_images);
 int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, unsigned* zbuf, DevBuf& djobs);
+// Render every job and score it against images [.][H][W] (device, img_of[j] (device) names job j's image) over masks [n_jobs][H][W]
+// (device): out [n_jobs] and, when inl is not null, inl [n_jobs][H][W] (device).  dz receives the z-buffers (asynchronous).
+int score_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, const float* images,
+               const int* img_of, const unsigned char* masks, unsigned char* inl, p2p_depth_score* out, DevBuf& dz, DevBuf& djobs);
+
+// The ICP inputs of p2p_icp_inputs_batch (normals.hip) left on the device: argument checks, records `out`, and the packed source /
+// target points (dsrc / dtgt, tot_src / tot_tgt points of 6 float32), the sensor frames dimg [slot][H][W] (slot_of[j]: job j's frame)
+// and the union masks dumask [n_jobs][H][W].  The caller releases the stage on every return.
+struct IcpInputsStage {
+    DevBuf dimg, dumask, dscene, dwork, ditems, dcmp, drow, dcmp2, drow2, dtgt, dsrc, dz, dj, dbox, dctgt, dcsrc, djob_of, dwork2, ditems2;
+    std::vector<int> slot_of;
+    int64_t tot_src = 0, tot_tgt = 0;
+    void release();
+};
+int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S);
 
 }  // namespace p2p

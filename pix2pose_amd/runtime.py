@@ -580,3 +580,80 @@ def icp_inputs_batch(ctx: Context, meshes, depths, jobs):
                     "centroid_src": np.array(r.centroid_src[:]), "centroid_tgt": np.array(r.centroid_tgt[:]),
                     "src": src[r.src_offset:r.src_offset + r.n_src].copy(), "tgt": tgt[r.tgt_offset:r.tgt_offset + r.n_tgt].copy()})
     return out
+
+
+def _icp_params(max_iterations=100, tolerance=0.005, rejection_scale=2.5, num_levels=2):
+    """cv2.ppf_match_3d_ICP(iterations, tolerence, rejectionScale, numLevels); the defaults are the reference's (icp3d.py:87)."""
+    p = _lib.IcpParams()
+    p.max_iterations, p.tolerance, p.rejection_scale, p.num_levels = int(max_iterations), tolerance, rejection_scale, int(num_levels)
+    return p
+
+
+def _icp_result(r):
+    return {"status": int(r.status), "iterations": list(r.iterations), "pairs": list(r.pairs), "fval_min": list(r.fval_min),
+            "scale": float(r.scale), "mean_avg": np.array(r.mean_avg[:]), "pose": np.array(r.pose[:]).reshape(4, 4)}
+
+
+def icp_batch(ctx: Context, inputs, src=None, tgt=None, **params):
+    """Point-to-plane ICP (p2p_icp_batch; the restatement of cv2.ppf_match_3d_ICP(...).registerModelToScene in DESIGN.md 8.2) of what
+    icp_inputs_batch returns: inputs is its list of dicts (each with 'status', 'src', 'tgt'); src / tgt may instead give every job's
+    point set [k, 6] explicitly.  params: max_iterations, tolerance, rejection_scale, num_levels (the reference's by default).
+    Returns one dict per job: status, iterations / pairs / fval_min per level (index = level, 0 the finest), scale, mean_avg and pose
+    (4 x 4, metres; identity when status != 0)."""
+    n = len(inputs)
+    src = [r["src"] for r in inputs] if src is None else src
+    tgt = [r["tgt"] for r in inputs] if tgt is None else tgt
+    if len(src) != n or len(tgt) != n:
+        raise ValueError("one source and one target set per job")
+    src = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 6)) for a in src]
+    tgt = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, 6)) for a in tgt]
+    recs = (_lib.IcpInput * max(1, n))()
+    so = to = 0
+    for k in range(n):
+        recs[k].status = int(inputs[k].get("status", 0))
+        recs[k].src_offset, recs[k].n_src, recs[k].tgt_offset, recs[k].n_tgt = so, len(src[k]), to, len(tgt[k])
+        so += len(src[k])
+        to += len(tgt[k])
+    sp = np.concatenate(src + [np.zeros((1, 6), np.float32)])
+    tp = np.concatenate(tgt + [np.zeros((1, 6), np.float32)])
+    p = _icp_params(**params)
+    res = (_lib.IcpResult * max(1, n))()
+    _lib.check(_lib.lib().p2p_icp_batch(ctx.handle, recs, n, sp.ctypes.data, tp.ctypes.data, C.byref(p), res), "p2p_icp_batch")
+    return [_icp_result(r) for r in res[:n]]
+
+
+def refine_depth_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = False, **params):
+    """The depth refinement of a frame's detections in one call (p2p_refine_depth_batch; icp3d.py:455-491): the ICP inputs of
+    icp_inputs_batch, the ICP of icp_batch, the refined pose and the depth score of depth_score_batch at that pose.  depths and jobs
+    as in icp_inputs_batch; params as in icp_batch.  Returns one dict per job: status (0, _lib.ICP_SMALL_BBOX / ICP_FEW_POINTS /
+    ICP_NONFINITE), R [3, 3] and t [3] (mm: the refined pose, or the job's own when status != 0), icp_pose (4 x 4, metres), iterations,
+    pairs, inlier_count, union_count, fcn, ratio (0 when status != 0) and the input record's fields (bbox, t_init, t_adjusted,
+    centroid_src, centroid_tgt, n_src, n_tgt); with inlier_masks=True also a bool array [n_jobs, H, W]."""
+    depths = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+    if not depths:
+        raise ValueError("refine_depth_batch needs at least one depth image")
+    H, W = depths[0].shape
+    if any(d.shape != (H, W) for d in depths):
+        raise ValueError("all depth images must have the same size")
+    for j in jobs:
+        if j.get("union_mask") is None or np.shape(j["union_mask"]) != (H, W):
+            raise ValueError("every job needs a union_mask of the depth images' size %r" % ((H, W),))
+    keep = []
+    arr = _depth_jobs(jobs, keep)
+    mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+    dp = (C.c_void_p * len(depths))(*[d.ctypes.data for d in depths])
+    p = _icp_params(**params)
+    res = (_lib.RefineResult * max(1, len(jobs)))()
+    masks = np.zeros((len(jobs), H, W), np.uint8) if inlier_masks else None
+    _lib.check(_lib.lib().p2p_refine_depth_batch(ctx.handle, mh, len(meshes), dp, len(depths), arr, len(jobs), H, W, C.byref(p), res,
+                                                 masks.ctypes.data if masks is not None else None), "p2p_refine_depth_batch")
+    out = []
+    for r in res[:len(jobs)]:
+        i, c = r.input, _icp_result(r.icp)
+        out.append({"status": c["status"], "R": np.array(r.R[:]).reshape(3, 3), "t": np.array(r.t[:]), "icp_pose": c["pose"],
+                    "iterations": c["iterations"], "pairs": c["pairs"], "fval_min": c["fval_min"],
+                    "inlier_count": int(r.score.inlier_count), "union_count": int(r.score.union_count), "fcn": float(r.score.fcn),
+                    "ratio": float(r.score.ratio), "bbox": list(i.bbox), "t_init": np.array(i.t_init[:]),
+                    "t_adjusted": np.array(i.t_adjusted[:]), "centroid_src": np.array(i.centroid_src[:]),
+                    "centroid_tgt": np.array(i.centroid_tgt[:]), "n_src": int(i.n_src), "n_tgt": int(i.n_tgt)})
+    return (out, masks.astype(bool)) if inlier_masks else out
