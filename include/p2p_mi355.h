@@ -560,6 +560,68 @@ P2P_API int p2p_refine_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, 
                                    int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width,
                                    const p2p_icp_params* params, p2p_refine_result* out, unsigned char* inlier_masks);
 
+/* ------------------------------------------------------------------------------------------
+ * RGB-D evaluation of an image chunk (csrc/rgbd.hip): the per-image loop of tools/5_evaluation_bop_icp3d.py
+ * :331-540 with its frames, detector masks, inlier masks and occupancy images kept on the device.  A handle holds one chunk.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct p2p_rgbd p2p_rgbd;
+
+typedef enum { P2P_DEPTH_U16 = 0, P2P_DEPTH_F32 = 1 } p2p_depth_dtype;
+
+/* Status of a refine record of p2p_rgbd_refine whose union det_mask & depth_valid has 30 pixels or fewer (icp3d.py:457-460): the job
+ * is not refined; its record keeps job.R / job.t, an identity icp.pose, a zero score and an all-zero inlier mask. */
+#define P2P_RGBD_SMALL_UNION (-4)
+
+/* Candidate codes of p2p_rgbd_resolve (cand_ref < 0) */
+#define P2P_RGBD_NOT_EVALUATED (-1)   /* not in the evaluated superset: the walk reaching it is an error (P2P_ERR_INVALID_ARG) */
+#define P2P_RGBD_EST_FAILED (-2)      /* est_pose status != 0 (frac_inlier == -1, :444-445) */
+#define P2P_RGBD_NEAR (-3)            /* est_pose t[2] / 1000 < 0.2 (:449-450) */
+
+P2P_API int p2p_rgbd_create(p2p_ctx* ctx, p2p_rgbd** out);
+/* Does not use the context: a handle may be destroyed after the context it was created on. */
+P2P_API void p2p_rgbd_destroy(p2p_rgbd* h);
+
+/* Load a chunk of n_images frames of height x width (replaces the chunk held before).  rgb[i]: host u8 [H][W][3] (gray frames
+ * replicated to three channels by the caller); depth[i]: host u16 or float32 [H][W] (depth_dtype) in the sensor's unit; depth_scale[i]
+ * from scene_camera.json.  On the device, per pixel and all in float32 without contraction (:360-370):
+ *   depth_t = (raw / 1000) * depth_scale,  depth_valid = depth_t > 0.2f && depth_t < 2.2f,
+ *   rgb_valid = depth_valid || nan_to_num(depth_t) == 0,  frame = rgb_valid ? float(rgb) : float(rgb) * 0.1f.
+ * masks: host u8 [n_masks][H][W] (nonzero = in), the detector masks of the chunk; mask_image[m] names the frame of mask m. */
+P2P_API int p2p_rgbd_load(p2p_rgbd* h, const unsigned char* const* rgb, const void* const* depth, int depth_dtype,
+                          const double* depth_scale, int n_images, int height, int width, const unsigned char* masks,
+                          const int* mask_image, int n_masks);
+/* The device frame i of the loaded chunk as a P2P_MEM_DEVICE, P2P_IMG_F32 p2p_image for p2p_est_pose_batch / _submit; valid until the
+ * next load or destroy. */
+P2P_API int p2p_rgbd_image(p2p_rgbd* h, int i, p2p_image* out);
+/* Copies of frame i's depth_t [H][W], depth_valid [H][W] (0 / 1) and frame [H][W][3] (host; each may be null). */
+P2P_API int p2p_rgbd_read(p2p_rgbd* h, int i, float* depth_t, unsigned char* depth_valid, float* frame);
+
+/* The depth refinement of p2p_refine_depth_batch with its inputs on the device: job k refines against depth_t of frame jobs[k].img_idx
+ * over the union mask det_mask[mask_idx[k]] & depth_valid (jobs[k].union_mask is ignored).  union_counts [n_jobs] (host) receives each
+ * union's pixel count; a union of 30 or fewer pixels gets a P2P_RGBD_SMALL_UNION record and is not refined.  Every other record and its
+ * inlier mask equal p2p_refine_depth_batch's on the same inputs bit for bit.  The records and inlier masks stay in the handle for
+ * p2p_rgbd_resolve (until the next refine or load); inlier_masks (host u8 [n_jobs][H][W], may be null) receives a copy.  A mask
+ * index outside the loaded masks, or one of another frame than the job's, is P2P_ERR_INVALID_ARG. */
+P2P_API int p2p_rgbd_refine(p2p_rgbd* h, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, const int* mask_idx,
+                            int n_jobs, const p2p_icp_params* params, p2p_refine_result* out, int64_t* union_counts,
+                            unsigned char* inlier_masks);
+
+/* One round (0 or 1) of the per-image walk (:394-510), one workgroup per image, occupancy images on the device (round 0 clears them).
+ *   images:     tgt_off [n_images + 1] into target_obj / inst_count (the image's targets, in order); roi_off [n_images + 1] into the rois.
+ *   rois:       roi_obj, roi_score (detector score), roi_valid (0 for a (-1, -1) roi), roi_mask (detector mask index of the loaded chunk);
+ *               cand_off [n_rois + 1] into the candidates of each roi.
+ *   candidates: cand_obj (object id) and cand_ref: the index of its refine record, or P2P_RGBD_NOT_EVALUATED / _EST_FAILED / _NEAR.
+ *   records:    those of the last p2p_rgbd_refine, or when host_records is not null, host_records [n_records] with host_masks
+ *               [n_records][H][W] (host u8, may be null: all-zero inlier masks).
+ * In / out: roi_used [n_rois] (0 / 1) and inst_pred [total targets] (the reference's roi_used and inst_count_pred; round 0 starts them
+ * at 0).  Out: rows [n_rois][16] = obj_id (0: no row), score, R[9], t[3] (mm), round, r_id -- a roi appends at most one row a round,
+ * so the rows of an image in roi order are its result list in append order.  A walk that reaches a NOT_EVALUATED candidate is
+ * P2P_ERR_INVALID_ARG. */
+P2P_API int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tgt_off, const int* target_obj, const int* inst_count,
+                             const int* roi_off, const int* roi_obj, const double* roi_score, const int* roi_valid, const int* roi_mask,
+                             const int* cand_off, const int* cand_obj, const int* cand_ref, const p2p_refine_result* host_records,
+                             const unsigned char* host_masks, int n_records, int* roi_used, int* inst_pred, double* rows);
+
 #ifdef __cplusplus
 }
 #endif

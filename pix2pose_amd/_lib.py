@@ -143,6 +143,10 @@ class RefineResult(C.Structure):
 ERR_CAPACITY = -4
 ICP_OK, ICP_SMALL_BBOX, ICP_FEW_POINTS = 0, -1, -2     # p2p_icp_input.status; both nonzero values are the reference's -1
 ICP_NONFINITE = -3                                     # p2p_icp_result.status: a non-finite source or target xyz
+DEPTH_U16, DEPTH_F32 = 0, 1                            # p2p_depth_dtype
+RGBD_SMALL_UNION = -4                                  # p2p_rgbd_refine record: union det_mask & depth_valid <= 30 pixels, not refined
+RGBD_NOT_EVALUATED, RGBD_EST_FAILED, RGBD_NEAR = -1, -2, -3     # p2p_rgbd_resolve candidate codes
+RGBD_ROW = 16                                          # p2p_rgbd_resolve row: obj_id, score, R[9], t[3], round, r_id
 
 
 _lib = None
@@ -289,6 +293,15 @@ def lib():
     L.p2p_icp_batch.argtypes = [vp, C.POINTER(IcpInput), ci, vp, vp, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     L.p2p_refine_depth_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci,
                                          C.POINTER(IcpParams), C.POINTER(RefineResult), vp]
+    L.p2p_rgbd_create.argtypes = [vp, C.POINTER(vp)]
+    L.p2p_rgbd_destroy.argtypes = [vp]
+    L.p2p_rgbd_destroy.restype = None
+    L.p2p_rgbd_load.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), ci, dp, ci, ci, ci, vp, C.POINTER(ci), ci]
+    L.p2p_rgbd_image.argtypes = [vp, ci, C.POINTER(Image)]
+    L.p2p_rgbd_read.argtypes = [vp, ci, vp, vp, vp]
+    L.p2p_rgbd_refine.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), C.POINTER(ci), ci, C.POINTER(IcpParams),
+                                  C.POINTER(RefineResult), vp, vp]
+    L.p2p_rgbd_resolve.argtypes = [vp, ci, ci] + [vp] * 11 + [C.POINTER(RefineResult), vp, ci, vp, vp, vp]
     _lib = L
     return L
 

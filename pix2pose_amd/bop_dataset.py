@@ -146,8 +146,10 @@ def group_detections(detections, model_ids):
     return out
 
 
-def build_dump(cfg: dict, dataset: str, detections) -> dict:
-    """The dict eval_bop.run() takes, with absolute paths, from the BOP directory cfg['dataset_dir'] and a detection list."""
+def build_dump(cfg: dict, dataset: str, detections, with_depth: bool = False) -> dict:
+    """The dict eval_bop.run() takes, with absolute paths, from the BOP directory cfg['dataset_dir'] and a detection list.
+    with_depth: also the keys eval_bop_icp.run() needs -- per image "depth" (``<test_dir>/<scene>/depth/<im>.png``, itodd ``.tif``)
+    and "depth_scale" (scene_camera.json), and "meshes" {obj id: ``obj_%06d.ply`` in the models directory} (tools/bop_io.py:121-135)."""
     bop_dir = cfg["dataset_dir"]
     dataset_dir, test_dir = dataset_dirs(bop_dir, dataset)
     model_ids = load_model_ids(dataset_dir, dataset, cfg.get("target_obj"))
@@ -173,8 +175,15 @@ def build_dump(cfg: dict, dataset: str, detections) -> dict:
               "rois": det["rois"], "obj_ids": det["obj_ids"], "scores": det["scores"]}
         if any(s is not None for s in det["segmentations"]):
             im["segmentations"] = det["segmentations"]
+        if with_depth:
+            im["depth"] = os.path.join(test_dir, "%06d" % sid, "depth", "%06d.%s" % (iid, "tif" if gray else "png"))
+            im["depth_scale"] = float(cams[sid][str(iid)]["depth_scale"])
         images.append(im)
-    return {"im_size": load_im_size(dataset_dir, dataset), "model_ids": model_ids,
+    dump = {"im_size": load_im_size(dataset_dir, dataset), "model_ids": model_ids,
             "norm_factor": {str(m): norm[str(m)] for m in model_ids},
             "weights": {str(m): weights_path(dataset_dir, m, backbone) for m in model_ids},
             "targets": targets, "images": images}
+    if with_depth:
+        mdir = _models_dir(dataset_dir, dataset)
+        dump["meshes"] = {str(m): os.path.join(mdir, "obj_%06d.ply" % m) for m in model_ids}
+    return dump

@@ -839,6 +839,95 @@ int icp_run(Ctx& X, const p2p_icp_input* in, int n_jobs, const float* S, const f
     return P2P_OK;
 }
 
+int refine_chain(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                 int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, const p2p_icp_params* params,
+                 p2p_refine_result* out, unsigned char* dinl, bool dev_inputs, DevBuf* dinl_alloc)
+{
+    if (!ctx || n_jobs < 0 || (n_jobs > 0 && !out)) {
+        set_error("%s: bad arguments", who);
+        return P2P_ERR_INVALID_ARG;
+    }
+    p2p_icp_params P;
+    int rc;
+    if ((rc = icp_check(who, params, nullptr, 0, P))) return rc;
+    std::vector<p2p_icp_input> in(std::max(n_jobs, 1));
+    IcpInputsStage S;
+    rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, in.data(), S, dev_inputs);
+    if (rc == P2P_OK && n_jobs > 0) rc = icp_check(who, params, in.data(), n_jobs, P);
+    if (rc || n_jobs == 0) {
+        S.release();
+        return rc;
+    }
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    hipStream_t st = c->stream;
+    std::vector<p2p_icp_result> icp(n_jobs);
+    if ((rc = icp_run(*c, in.data(), n_jobs, S.dsrc.as<float>(), S.dtgt.as<float>(), P, icp.data()))) {
+        S.release();
+        return rc;
+    }
+    // tf = pose * [R | t_adjusted / 1000] (icp_refinement :91-93), R_ref = tf[:3,:3], t_ref = tf[:3,3] * 1000 (:466-467)
+    std::vector<p2p_refine_job> rj(jobs, jobs + n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        p2p_refine_result& R = out[j];
+        std::memset(&R, 0, sizeof(R));
+        R.input = in[j];
+        R.icp = icp[j];
+        if (icp[j].status != 0) {
+            for (int k = 0; k < 9; ++k) R.R[k] = jobs[j].R[k];
+            for (int k = 0; k < 3; ++k) R.t[k] = jobs[j].t[k];
+            continue;
+        }
+        double tf0[16] = {0}, tf[16];
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) tf0[4 * r + k] = jobs[j].R[3 * r + k];
+            tf0[4 * r + 3] = in[j].t_adjusted[r] / 1000.0;
+        }
+        tf0[15] = 1.0;
+        const double* A = icp[j].pose;
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                double s = A[4 * a] * tf0[b];
+                for (int k = 1; k < 4; ++k) s = s + A[4 * a + k] * tf0[4 * k + b];
+                tf[4 * a + b] = s;
+            }
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 3; ++k) R.R[3 * r + k] = rj[j].R[3 * r + k] = tf[4 * r + k];
+            R.t[r] = rj[j].t[r] = tf[4 * r + 3] * 1000.0;
+        }
+    }
+    // the score at the refined pose (the frames and union masks of the stage; every job is scored, the gated ones are zeroed below)
+    const size_t HW = (size_t)height * width;
+    DevBuf dof, dout, dz, dj;
+    auto cleanup = [&]() { S.release(); dof.release(); dout.release(); dz.release(); dj.release(); };
+    if ((rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
+        (dinl_alloc && (rc = dinl_alloc->reserve(n_jobs * HW)))) {
+        cleanup();
+        return rc;
+    }
+    if (dinl_alloc) dinl = dinl_alloc->as<unsigned char>();
+    std::vector<p2p_depth_score> sc(n_jobs);
+    hipError_t e = hipMemcpyAsync(dof.p, S.slot_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess &&
+        (rc = score_into(*c, meshes, rj.data(), n_jobs, height, width, S.dimg.as<float>(), dof.as<int>(), S.dumask.as<unsigned char>(),
+                         dinl, dout.as<p2p_depth_score>(), dz, dj))) {
+        cleanup();
+        return rc;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(sc.data(), dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st);
+    for (int j = 0; j < n_jobs && e == hipSuccess && dinl; ++j)
+        if (icp[j].status != 0) e = hipMemsetAsync(dinl + j * HW, 0, HW, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    cleanup();
+    if (e != hipSuccess) {
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return P2P_ERR_HIP;
+    }
+    for (int j = 0; j < n_jobs; ++j)
+        if (icp[j].status == 0) out[j].score = sc[j];
+    return P2P_OK;
+}
+
+
 }  // namespace p2p
 
 using namespace p2p;
@@ -892,91 +981,20 @@ int p2p_refine_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_me
                            p2p_refine_result* out, unsigned char* inlier_masks)
 {
     const char* who = "p2p_refine_depth_batch";
-    if (!ctx || n_jobs < 0 || (n_jobs > 0 && !out)) {
-        set_error("%s: bad arguments", who);
-        return P2P_ERR_INVALID_ARG;
-    }
-    p2p_icp_params P;
-    int rc;
-    if ((rc = icp_check(who, params, nullptr, 0, P))) return rc;
-    std::vector<p2p_icp_input> in(std::max(n_jobs, 1));
-    IcpInputsStage S;
-    rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, in.data(), S);
-    if (rc == P2P_OK && n_jobs > 0) rc = icp_check(who, params, in.data(), n_jobs, P);
-    if (rc || n_jobs == 0) {
-        S.release();
-        return rc;
-    }
-    Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    hipStream_t st = c->stream;
-    std::vector<p2p_icp_result> icp(n_jobs);
-    if ((rc = icp_run(*c, in.data(), n_jobs, S.dsrc.as<float>(), S.dtgt.as<float>(), P, icp.data()))) {
-        S.release();
-        return rc;
-    }
-    // tf = pose * [R | t_adjusted / 1000] (icp_refinement :91-93), R_ref = tf[:3,:3], t_ref = tf[:3,3] * 1000 (:466-467)
-    std::vector<p2p_refine_job> rj(jobs, jobs + n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        p2p_refine_result& R = out[j];
-        std::memset(&R, 0, sizeof(R));
-        R.input = in[j];
-        R.icp = icp[j];
-        if (icp[j].status != 0) {
-            for (int k = 0; k < 9; ++k) R.R[k] = jobs[j].R[k];
-            for (int k = 0; k < 3; ++k) R.t[k] = jobs[j].t[k];
-            continue;
-        }
-        double tf0[16] = {0}, tf[16];
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) tf0[4 * r + k] = jobs[j].R[3 * r + k];
-            tf0[4 * r + 3] = in[j].t_adjusted[r] / 1000.0;
-        }
-        tf0[15] = 1.0;
-        const double* A = icp[j].pose;
-        for (int a = 0; a < 4; ++a)
-            for (int b = 0; b < 4; ++b) {
-                double s = A[4 * a] * tf0[b];
-                for (int k = 1; k < 4; ++k) s = s + A[4 * a + k] * tf0[4 * k + b];
-                tf[4 * a + b] = s;
-            }
-        for (int r = 0; r < 3; ++r) {
-            for (int k = 0; k < 3; ++k) R.R[3 * r + k] = rj[j].R[3 * r + k] = tf[4 * r + k];
-            R.t[r] = rj[j].t[r] = tf[4 * r + 3] * 1000.0;
+    DevBuf dinl;       // the inlier masks on the device, allocated by the chain once its checks have passed
+    int rc = refine_chain(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, params, out, nullptr, false,
+                          inlier_masks ? &dinl : nullptr);
+    if (rc == P2P_OK && inlier_masks && n_jobs > 0) {
+        hipStream_t st = reinterpret_cast<Ctx*>(ctx)->stream;
+        hipError_t e = hipMemcpyAsync(inlier_masks, dinl.p, (size_t)n_jobs * height * width, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            set_error("%s: %s", who, hipGetErrorString(e));
+            rc = P2P_ERR_HIP;
         }
     }
-    // the score at the refined pose (the frames and union masks of the stage; every job is scored, the gated ones are zeroed below)
-    const size_t HW = (size_t)height * width;
-    DevBuf dof, dout, dinl, dz, dj;
-    auto cleanup = [&]() { S.release(); dof.release(); dout.release(); dinl.release(); dz.release(); dj.release(); };
-    if ((rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
-        (inlier_masks && (rc = dinl.reserve(n_jobs * HW)))) {
-        cleanup();
-        return rc;
-    }
-    std::vector<p2p_depth_score> sc(n_jobs);
-    hipError_t e = hipMemcpyAsync(dof.p, S.slot_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess &&
-        (rc = score_into(*c, meshes, rj.data(), n_jobs, height, width, S.dimg.as<float>(), dof.as<int>(), S.dumask.as<unsigned char>(),
-                         inlier_masks ? dinl.as<unsigned char>() : nullptr, dout.as<p2p_depth_score>(), dz, dj))) {
-        cleanup();
-        return rc;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(sc.data(), dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && inlier_masks) e = hipMemcpyAsync(inlier_masks, dinl.p, n_jobs * HW, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    }
-    for (int j = 0; j < n_jobs; ++j) {
-        if (icp[j].status == 0) {
-            out[j].score = sc[j];
-        } else if (inlier_masks) {
-            std::memset(inlier_masks + j * HW, 0, HW);
-        }
-    }
-    return P2P_OK;
+    dinl.release();
+    return rc;
 }
 
 }  // extern "C"

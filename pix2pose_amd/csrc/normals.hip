@@ -421,7 +421,7 @@ NrmItem frame_item(const float* depth, const double* K, int H, int W)
 // Scene points of n frames: uploads depth_images[img[f]] and runs fill, Gaussian and normals with camera cams[f] into dpts
 // [n][H][W][6] (asynchronous).
 int frame_points(hipStream_t st, const float* const* depth_images, const int* img, const double* const* cams, int n, int H, int W,
-                 DevBuf& dimg, DevBuf& dpts, DevBuf& dwork, DevBuf& ditems)
+                 DevBuf& dimg, DevBuf& dpts, DevBuf& dwork, DevBuf& ditems, bool dev_inputs = false)
 {
     const size_t HW = (size_t)H * W;
     int rc;
@@ -433,7 +433,8 @@ int frame_points(hipStream_t st, const float* const* depth_images, const int* im
     }
     if ((rc = alloc_items(items, dwork, false)) || (rc = ditems.reserve(sizeof(NrmItem) * n))) return rc;
     for (int f = 0; f < n; ++f)
-        NRM_TRY(hipMemcpyAsync(dimg.as<float>() + f * HW, depth_images[img[f]], HW * 4, hipMemcpyHostToDevice, st));
+        NRM_TRY(hipMemcpyAsync(dimg.as<float>() + f * HW, depth_images[img[f]], HW * 4,
+                               dev_inputs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
     NRM_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(NrmItem) * n, hipMemcpyHostToDevice, st));
     return run_items(st, items, ditems.as<NrmItem>(), H, W);
 }
@@ -526,7 +527,8 @@ void IcpInputsStage::release()
 }
 
 int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
-                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S)
+                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S,
+                     bool dev_inputs)
 {
     if (!ctx || n_jobs < 0 || n_jobs > 65535 || n_images < 0 || (n_jobs > 0 && (!meshes || !jobs || !out || !depth_images))) {
         set_error("%s: bad arguments", who);
@@ -584,10 +586,11 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
     const int nf = (int)frames.size();
     std::vector<const double*> cams(nf);
     for (int f = 0; f < nf; ++f) cams[f] = jobs[frame_job[f]].camK;
-    NRM_STEP(frame_points(st, depth_images, frames.data(), cams.data(), nf, height, width, dimg, dscene, dwork, ditems));
+    NRM_STEP(frame_points(st, depth_images, frames.data(), cams.data(), nf, height, width, dimg, dscene, dwork, ditems, dev_inputs));
     NRM_STEP(dumask.reserve(n_jobs * HW));
     for (int j = 0; j < n_jobs; ++j)
-        NRM_STEP(hip(hipMemcpyAsync(dumask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW, hipMemcpyHostToDevice, st)));
+        NRM_STEP(hip(hipMemcpyAsync(dumask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW,
+                                    dev_inputs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st)));
 
     // 2. target points pts_tgt = points_tgt[union_mask] (:464) and their centroid (icp_refinement :59)
     std::vector<CmpItem> titems(n_jobs);

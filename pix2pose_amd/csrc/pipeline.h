@@ -216,7 +216,8 @@ int score_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs
 
 // The ICP inputs of p2p_icp_inputs_batch (normals.hip) left on the device: argument checks, records `out`, and the packed source /
 // target points (dsrc / dtgt, tot_src / tot_tgt points of 6 float32), the sensor frames dimg [slot][H][W] (slot_of[j]: job j's frame)
-// and the union masks dumask [n_jobs][H][W].  The caller releases the stage on every return.
+// and the union masks dumask [n_jobs][H][W].  The caller releases the stage on every return.  dev_inputs: depth_images and the jobs'
+// union_mask pointers are device memory (rgbd.hip), copied on the device; otherwise host memory.
 struct IcpInputsStage {
     DevBuf dimg, dumask, dscene, dwork, ditems, dcmp, drow, dcmp2, drow2, dtgt, dsrc, dz, dj, dbox, dctgt, dcsrc, djob_of, dwork2, ditems2;
     std::vector<int> slot_of;
@@ -224,6 +225,13 @@ struct IcpInputsStage {
     void release();
 };
 int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
-                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S);
+                     int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S,
+                     bool dev_inputs = false);
+// The chain of p2p_refine_depth_batch (icp.hip) with its argument checks: records `out`; inlier masks [n_jobs][H][W] into the DEVICE
+// buffer dinl when it is not null (all 0 for a job whose status is not 0), left there; with dinl_alloc, into that buffer, sized once the
+// checks have passed.  dev_inputs as in icp_inputs_stage.
+int refine_chain(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
+                 int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, const p2p_icp_params* params,
+                 p2p_refine_result* out, unsigned char* dinl, bool dev_inputs, DevBuf* dinl_alloc = nullptr);
 
 }  // namespace p2p

@@ -657,3 +657,136 @@ def refine_depth_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = 
                     "t_adjusted": np.array(i.t_adjusted[:]), "centroid_src": np.array(i.centroid_src[:]),
                     "centroid_tgt": np.array(i.centroid_tgt[:]), "n_src": int(i.n_src), "n_tgt": int(i.n_tgt)})
     return (out, masks.astype(bool)) if inlier_masks else out
+
+
+def _refine_record(r):
+    i, c = r.input, _icp_result(r.icp)
+    return {"status": c["status"], "R": np.array(r.R[:]).reshape(3, 3), "t": np.array(r.t[:]), "icp_pose": c["pose"],
+            "iterations": c["iterations"], "pairs": c["pairs"], "fval_min": c["fval_min"],
+            "inlier_count": int(r.score.inlier_count), "union_count": int(r.score.union_count), "fcn": float(r.score.fcn),
+            "ratio": float(r.score.ratio), "bbox": list(i.bbox), "t_init": np.array(i.t_init[:]),
+            "t_adjusted": np.array(i.t_adjusted[:]), "centroid_src": np.array(i.centroid_src[:]),
+            "centroid_tgt": np.array(i.centroid_tgt[:]), "n_src": int(i.n_src), "n_tgt": int(i.n_tgt)}
+
+
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+
+
+class Rgbd:
+    """One image chunk of the RGB-D evaluation on the device (p2p_rgbd, csrc/rgbd.hip): prepared frames, detector masks, the inlier
+    masks of the last refine and one occupancy image per frame."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().p2p_rgbd_create(ctx.handle, C.byref(self._h)), "p2p_rgbd_create")
+        self.n_images, self.H, self.W = 0, 0, 0
+
+    def load(self, rgbs, depths, depth_scales, masks, mask_image):
+        """rgbs: [H, W, 3] u8 frames; depths: [H, W] uint16 or float32 (all the same dtype); masks: [n, H, W] detector masks (nonzero
+        = in), mask_image[m] = frame of mask m."""
+        n = len(rgbs)
+        rgbs = [np.ascontiguousarray(r, dtype=np.uint8) for r in rgbs]
+        dts = {np.asarray(d).dtype for d in depths}
+        if dts <= {np.dtype(np.uint16)}:
+            code, depths = _lib.DEPTH_U16, [np.ascontiguousarray(d, dtype=np.uint16) for d in depths]
+        elif dts <= {np.dtype(np.float32)}:
+            code, depths = _lib.DEPTH_F32, [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+        else:
+            raise ValueError("depth frames must all be uint16 or all float32, got %r" % sorted(str(d) for d in dts))
+        H, W = depths[0].shape if n else (0, 0)
+        if any(r.shape != (H, W, 3) for r in rgbs) or any(d.shape != (H, W) for d in depths):
+            raise ValueError("every frame must be %r x 3 and every depth %r" % ((H, W), (H, W)))
+        m = np.ascontiguousarray(np.asarray(masks) != 0, dtype=np.uint8).reshape(-1, H, W) if len(masks) else np.zeros((0, H, W), np.uint8)
+        mi = _i32(mask_image)
+        sc = np.ascontiguousarray(depth_scales, dtype=np.float64)
+        rp = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in rgbs])
+        dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in depths])
+        _lib.check(_lib.lib().p2p_rgbd_load(self._h, rp, dp, code, sc.ctypes.data_as(C.POINTER(C.c_double)), n, H, W,
+                                            m.ctypes.data if m.size else None, mi.ctypes.data_as(C.POINTER(C.c_int)), len(m)),
+                   "p2p_rgbd_load")
+        self.n_images, self.H, self.W = n, H, W
+
+    def image(self, i):
+        """Frame i as est_pose_batch / est_pose_submit take a device frame: (pointer, H, W, 'f32')."""
+        s = _lib.Image()
+        _lib.check(_lib.lib().p2p_rgbd_image(self._h, i, C.byref(s)), "p2p_rgbd_image")
+        return (s.data, s.height, s.width, "f32")
+
+    def read(self, i):
+        """-> (depth_t [H, W] float32, depth_valid [H, W] bool, frame [H, W, 3] float32) of frame i."""
+        d = np.zeros((self.H, self.W), np.float32)
+        v = np.zeros((self.H, self.W), np.uint8)
+        f = np.zeros((self.H, self.W, 3), np.float32)
+        _lib.check(_lib.lib().p2p_rgbd_read(self._h, i, d.ctypes.data, v.ctypes.data, f.ctypes.data), "p2p_rgbd_read")
+        return d, v.astype(bool), f
+
+    def refine(self, meshes, jobs, mask_idx, inlier_masks=False, raw=False, **params):
+        """jobs: dicts image (frame), mesh, camK, R, t (mm) as in refine_depth_batch, without union_mask; mask_idx[k]: the detector mask
+        of job k.  -> (records as refine_depth_batch returns them, union counts [n] int64[, inlier masks [n, H, W] bool]).  raw=True
+        returns the _lib.RefineResult array instead of dicts."""
+        n = len(jobs)
+        jj = [dict(j, union_mask=None) for j in jobs]
+        arr = (_lib.RefineJob * max(1, n))()
+        for k, j in enumerate(jj):
+            J = arr[k]
+            J.img_idx, J.mesh_idx = int(j.get("image", 0)), int(j["mesh"])
+            J.camK[:] = [float(v) for v in np.asarray(j["camK"], np.float64).reshape(9)]
+            J.R[:] = [float(v) for v in np.asarray(j["R"], np.float64).reshape(9)]
+            J.t[:] = [float(v) for v in np.asarray(j["t"], np.float64).reshape(3)]
+            J.union_mask = None
+        mi = _i32(mask_idx) if n else np.zeros(1, np.int32)
+        mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+        p = _icp_params(**params)
+        res = (_lib.RefineResult * max(1, n))()
+        cnt = np.zeros(max(n, 1), np.int64)
+        masks = np.zeros((n, self.H, self.W), np.uint8) if inlier_masks else None
+        _lib.check(_lib.lib().p2p_rgbd_refine(self._h, mh, len(meshes), arr, mi.ctypes.data_as(C.POINTER(C.c_int)), n, C.byref(p), res,
+                                              cnt.ctypes.data, masks.ctypes.data if masks is not None and n else None), "p2p_rgbd_refine")
+        recs = res if raw else [_refine_record(r) for r in res[:n]]
+        out = (recs, cnt[:n])
+        return out + (masks.astype(bool),) if inlier_masks else out
+
+    def resolve(self, rnd, images, roi_used, inst_pred, host_records=None, host_masks=None):
+        """One round of the walk (p2p_rgbd_resolve).  images: per frame a dict targets [obj ids], inst_counts, rois: list of dicts
+        obj, score, valid, mask, cands: list of (obj id, ref) with ref a record index or _lib.RGBD_* code.  roi_used / inst_pred:
+        flat int32 arrays (rois, targets in image order), updated in place.  host_records: a _lib.RefineResult array (substitutes the
+        last refine's records), host_masks: its inlier masks [n, H, W].  -> rows [n_rois, 16]."""
+        tgt_off, tobj, tcnt, roi_off, robj, rsc, rval, rmask, coff, cobj, cref = [0], [], [], [0], [], [], [], [], [0], [], []
+        for im in images:
+            tobj += list(im["targets"]); tcnt += list(im["inst_counts"]); tgt_off.append(len(tobj))
+            for r in im["rois"]:
+                robj.append(r["obj"]); rsc.append(float(r["score"])); rval.append(1 if r["valid"] else 0); rmask.append(r["mask"])
+                for o, ref in r["cands"]:
+                    cobj.append(o); cref.append(ref)
+                coff.append(len(cobj))
+            roi_off.append(len(robj))
+        a = [_i32(x) for x in (tgt_off, tobj, tcnt, roi_off, robj)]
+        rs = np.ascontiguousarray(rsc, dtype=np.float64)
+        b = [_i32(x) for x in (rval, rmask, coff, cobj, cref)]
+        nr = len(robj)
+        rows = np.zeros((max(nr, 1), _lib.RGBD_ROW), np.float64)
+        if roi_used.dtype != np.int32 or inst_pred.dtype != np.int32:
+            raise ValueError("roi_used and inst_pred must be int32 arrays")
+        hm, n_rec = None, 0
+        if host_records is not None:
+            n_rec = len(host_records)
+            if host_masks is not None:
+                hm = np.ascontiguousarray(np.asarray(host_masks) != 0, dtype=np.uint8)
+        ptr = lambda x: x.ctypes.data if x.size else None      # noqa: E731
+        _lib.check(_lib.lib().p2p_rgbd_resolve(self._h, int(rnd), len(images), *[ptr(x) for x in a], ptr(rs), *[ptr(x) for x in b],
+                                               host_records, hm.ctypes.data if hm is not None and hm.size else None, n_rec,
+                                               ptr(roi_used), ptr(inst_pred), rows.ctypes.data), "p2p_rgbd_resolve")
+        return rows[:nr]
+
+    def close(self):
+        if self._h:
+            _lib.lib().p2p_rgbd_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
