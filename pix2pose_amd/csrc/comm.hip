@@ -21,15 +21,6 @@
 
 namespace p2p {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 struct Rccl {
     void* handle = nullptr;
     decltype(&ncclGetUniqueId) get_unique_id = nullptr;
@@ -84,10 +75,9 @@ struct Comm {
     PinnedBuf h_recv;
     hipStream_t stream = nullptr;      // the gathers run here
     hipEvent_t landed = nullptr;       // behind the D2H copy of a gather
-    ~Comm()
+    ~Comm()      // send / recv / h_recv free themselves after this body
     {
         if (comm && lib) (void)lib->comm_destroy(comm);
-        send.release(); recv.release(); h_recv.release();
         if (landed) hipEventDestroy(landed);
         if (stream) hipStreamDestroy(stream);
     }

@@ -24,15 +24,6 @@ namespace p2p {
 
 namespace {
 
-#define DEPTH_TRY(expr)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 constexpr double CLIP_NEAR = 0.01, CLIP_FAR = 10.0;      // Renderer.set_cam defaults (renderer_xyz.py:126)
 constexpr unsigned DEPTH_EMPTY = 0x7f800000u;            // +inf: above every finite depth in the atomicMin order of positive floats
 constexpr int RASTER_THREADS = 256, SCORE_THREADS = 256;
@@ -254,19 +245,19 @@ int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* job
     unsigned* n_big = reinterpret_cast<unsigned*>(djobs.as<char>() + jb);
     int2* big = reinterpret_cast<int2*>(djobs.as<char>() + jb + 256);
     const size_t n = (size_t)n_jobs * H * W;
-    DEPTH_TRY(hipMemcpyAsync(dj, rj.data(), sizeof(RasterJob) * n_jobs, hipMemcpyHostToDevice, st));
-    DEPTH_TRY(hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
-    DEPTH_TRY(hipMemsetD32Async((hipDeviceptr_t)zbuf, (int)DEPTH_EMPTY, n, st));
+    HIP_TRY(hipMemcpyAsync(dj, rj.data(), sizeof(RasterJob) * n_jobs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)zbuf, (int)DEPTH_EMPTY, n, st));
     if (max_tris > 0) {
         dim3 grid((max_tris + RASTER_THREADS - 1) / RASTER_THREADS, n_jobs);
         depth_raster_kernel<<<grid, RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
-        DEPTH_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         depth_raster_big_kernel<<<(unsigned)std::min<size_t>(cap, 1024), RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
-        DEPTH_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
     depth_finish_kernel<<<blocks, 256, 0, st>>>(zbuf, n);
-    DEPTH_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return P2P_OK;
 }
 
@@ -277,7 +268,7 @@ int score_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs
     int rc;
     if ((rc = dz.reserve(n_jobs * HW * 4)) || (rc = render_into(X, meshes, jobs, n_jobs, H, W, dz.as<unsigned>(), djobs))) return rc;
     depth_score_kernel<<<n_jobs, SCORE_THREADS, 0, X.stream>>>(dz.as<float>(), images, img_of, masks, (int)HW, inl, out);
-    DEPTH_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return P2P_OK;
 }
 
@@ -300,7 +291,7 @@ int p2p_mesh_create(p2p_ctx* ctx, const float* verts_mm, int n_verts, const int*
             return P2P_ERR_INVALID_ARG;
         }
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    DEPTH_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     std::vector<float> vm((size_t)n_verts * 3);
     for (size_t k = 0; k < vm.size(); ++k) vm[k] = verts_mm[k] * 0.001f;     // float32 x float32, as numpy scales a float32 cloud
     p2p_mesh* M = new p2p_mesh;
@@ -338,22 +329,12 @@ int p2p_render_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_me
     if ((rc = check_jobs("p2p_render_depth_batch", meshes, n_meshes, jobs, n_jobs, height, width, -1))) return rc;
     if (n_jobs == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    DEPTH_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)n_jobs * height * width;
     DevBuf dz, dj;
-    auto cleanup = [&]() { dz.release(); dj.release(); };
-    if ((rc = dz.reserve(n * 4)) || (rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) {
-        cleanup();
-        return rc;
-    }
-    hipError_t e;
-    if ((e = hipMemcpyAsync(depth, dz.p, n * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-        set_error("p2p_render_depth_batch: %s", hipGetErrorString(e));
-        cleanup();
-        return P2P_ERR_HIP;
-    }
-    cleanup();
+    if ((rc = dz.reserve(n * 4)) || (rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) return rc;
+    HIP_TRY(hipMemcpyAsync(depth, dz.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return P2P_OK;
 }
 
@@ -373,43 +354,27 @@ int p2p_depth_score_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mes
         }
     if (n_jobs == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    DEPTH_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t HW = (size_t)height * width;
     DevBuf dz, dj, dimg, dmask, dof, dinl, dout;
-    auto cleanup = [&]() { dz.release(); dj.release(); dimg.release(); dmask.release(); dof.release(); dinl.release(); dout.release(); };
     if ((rc = dimg.reserve(n_images * HW * 4)) || (rc = dmask.reserve(n_jobs * HW)) ||
         (rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
-        (inlier_masks && (rc = dinl.reserve(n_jobs * HW)))) {
-        cleanup();
+        (inlier_masks && (rc = dinl.reserve(n_jobs * HW))))
         return rc;
-    }
     std::vector<int> img_of(n_jobs);
     for (int j = 0; j < n_jobs; ++j) img_of[j] = jobs[j].img_idx;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n_images && e == hipSuccess; ++i)
-        e = hipMemcpyAsync(dimg.as<float>() + i * HW, depth_images[i], HW * 4, hipMemcpyHostToDevice, st);
-    for (int j = 0; j < n_jobs && e == hipSuccess; ++j)
-        e = hipMemcpyAsync(dmask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dof.p, img_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-        set_error("p2p_depth_score_batch: %s", hipGetErrorString(e));
-        cleanup();
-        return P2P_ERR_HIP;
-    }
+    for (int i = 0; i < n_images; ++i)
+        HIP_TRY(hipMemcpyAsync(dimg.as<float>() + i * HW, depth_images[i], HW * 4, hipMemcpyHostToDevice, st));
+    for (int j = 0; j < n_jobs; ++j)
+        HIP_TRY(hipMemcpyAsync(dmask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dof.p, img_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st));
     if ((rc = score_into(*c, meshes, jobs, n_jobs, height, width, dimg.as<float>(), dof.as<int>(), dmask.as<unsigned char>(),
-                         inlier_masks ? dinl.as<unsigned char>() : nullptr, dout.as<p2p_depth_score>(), dz, dj))) {
-        cleanup();
+                         inlier_masks ? dinl.as<unsigned char>() : nullptr, dout.as<p2p_depth_score>(), dz, dj)))
         return rc;
-    }
-    if ((e = hipMemcpyAsync(out, dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (inlier_masks && (e = hipMemcpyAsync(inlier_masks, dinl.p, n_jobs * HW, hipMemcpyDeviceToHost, st)) != hipSuccess) ||
-        (e = hipStreamSynchronize(st)) != hipSuccess) {
-        set_error("p2p_depth_score_batch: %s", hipGetErrorString(e));
-        cleanup();
-        return P2P_ERR_HIP;
-    }
-    cleanup();
+    HIP_TRY(hipMemcpyAsync(out, dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st));
+    if (inlier_masks) HIP_TRY(hipMemcpyAsync(inlier_masks, dinl.p, n_jobs * HW, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 

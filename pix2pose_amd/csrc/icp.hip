@@ -23,15 +23,6 @@ namespace p2p {
 
 namespace {
 
-#define ICP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 constexpr int PT_THREADS = 256;        // per-point kernels
 constexpr int JOB_THREADS = 256;       // one workgroup per job
 constexpr int CHECK_EVERY = 4;         // iterations queued between two reads of the active-job count (measured)
@@ -735,10 +726,6 @@ int icp_run(Ctx& X, const p2p_icp_input* in, int n_jobs, const float* S, const f
         }
     }
     DevBuf djobs, dlv, dS0, dT0, dP, dM, dQ, dqs, dqcell, dkeys, djidx, dd2, dcnt, dstart, dcur, dact;
-    auto cleanup = [&]() {
-        for (DevBuf* b : {&djobs, &dlv, &dS0, &dT0, &dP, &dM, &dQ, &dqs, &dqcell, &dkeys, &djidx, &dd2, &dcnt, &dstart, &dcur, &dact})
-            b->release();
-    };
     int rc;
     const int64_t nn = std::max<int64_t>(tot_n, 1), mm = std::max<int64_t>(tot_m, 1), cells = tot_m + 2 * (int64_t)n_jobs + 1;
     int max_iters = 1;
@@ -747,47 +734,36 @@ int icp_run(Ctx& X, const p2p_icp_input* in, int n_jobs, const float* S, const f
         (rc = dS0.reserve(nn * 24)) || (rc = dT0.reserve(mm * 24)) || (rc = dP.reserve(nn * 24)) || (rc = dM.reserve(nn * 16)) ||
         (rc = dQ.reserve(mm * 24)) || (rc = dqs.reserve(mm * 16)) || (rc = dqcell.reserve(mm * 4)) || (rc = dkeys.reserve(mm * 8)) ||
         (rc = djidx.reserve(nn * 4)) || (rc = dd2.reserve(nn * 4)) || (rc = dcnt.reserve(cells * 4)) || (rc = dstart.reserve(cells * 4)) ||
-        (rc = dcur.reserve(cells * 4)) || (rc = dact.reserve(sizeof(int) * (L * (size_t)max_iters)))) {
-        cleanup();
+        (rc = dcur.reserve(cells * 4)) || (rc = dact.reserve(sizeof(int) * (L * (size_t)max_iters))))
         return rc;
-    }
-#define ICP_STEP(expr)                                    \
-    do {                                                  \
-        hipError_t e_ = (expr);                           \
-        if (e_ != hipSuccess) {                           \
-            set_error("p2p icp: %s", hipGetErrorString(e_)); \
-            cleanup();                                    \
-            return P2P_ERR_HIP;                           \
-        }                                                 \
-    } while (0)
     IcpJob* J = djobs.as<IcpJob>();
-    ICP_STEP(hipMemcpyAsync(J, hj.data(), sizeof(IcpJob) * n_jobs, hipMemcpyHostToDevice, st));
-    ICP_STEP(hipMemcpyAsync(dlv.p, lv.data(), sizeof(IcpLevel) * lv.size(), hipMemcpyHostToDevice, st));
-    ICP_STEP(hipMemsetAsync(dact.p, 0, sizeof(int) * (L * (size_t)max_iters), st));
+    HIP_TRY(hipMemcpyAsync(J, hj.data(), sizeof(IcpJob) * n_jobs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dlv.p, lv.data(), sizeof(IcpLevel) * lv.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dact.p, 0, sizeof(int) * (L * (size_t)max_iters), st));
     // (the caller's arrays are read in place through the input offsets; S0 / T0 are packed without the gaps of status != 0 records)
     icp_stats_kernel<<<n_jobs, 64, 0, st>>>(J, S, T);
-    ICP_STEP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     icp_normalise_kernel<<<dim3((std::max(max_n, max_m) + PT_THREADS - 1) / PT_THREADS, n_jobs, 2), PT_THREADS, 0, st>>>(
         J, S, T, dS0.as<float>(), dT0.as<float>());
-    ICP_STEP(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     const unsigned jb = (unsigned)((n_jobs + 63) / 64);
     std::vector<int> act(1);
     for (int li = 0; li < L; ++li) {
         icp_level_kernel<<<jb, 64, 0, st>>>(J, n_jobs, dlv.as<IcpLevel>() + (size_t)li * n_jobs, L - 1 - li);
-        ICP_STEP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         const dim3 gp((max_np[li] + PT_THREADS - 1) / PT_THREADS, n_jobs), gq((max_nq[li] + PT_THREADS - 1) / PT_THREADS, n_jobs);
         const dim3 gs(std::max(gp.x, gq.x), n_jobs, 2);
         icp_sample_kernel<<<gs, PT_THREADS, 0, st>>>(J, dS0.as<float>(), dT0.as<float>(), dP.as<float>(), dM.as<float4>(), dQ.as<float>());
-        ICP_STEP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (!brute) {
             icp_grid_bbox_kernel<<<n_jobs, JOB_THREADS, 0, st>>>(J, dQ.as<float>(), dcnt.as<int>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_grid_count_kernel<<<gq, PT_THREADS, 0, st>>>(J, dQ.as<float>(), dqcell.as<int>(), dcnt.as<int>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_grid_scan_kernel<<<n_jobs, JOB_THREADS, 0, st>>>(J, dcnt.as<int>(), dstart.as<int>(), dcur.as<int>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_grid_scatter_kernel<<<gq, PT_THREADS, 0, st>>>(J, dQ.as<float>(), dqcell.as<int>(), dcur.as<int>(), dqs.as<float4>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         int* actv = dact.as<int>() + (size_t)li * max_iters;
         for (int it = 0; it < max_it[li]; ++it) {
@@ -796,30 +772,28 @@ int icp_run(Ctx& X, const p2p_icp_input* in, int n_jobs, const float* S, const f
             else
                 icp_nn_grid_kernel<<<gp, PT_THREADS, 0, st>>>(J, dM.as<float4>(), dqs.as<float4>(), dstart.as<int>(), djidx.as<int>(),
                                                              dd2.as<float>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_select_kernel<<<n_jobs, JOB_THREADS, 0, st>>>(J, dd2.as<float>(), dkeys.as<unsigned long long>(), P.rejection_scale);
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_picky_kernel<<<gp, PT_THREADS, 0, st>>>(J, djidx.as<int>(), dd2.as<float>(), dkeys.as<unsigned long long>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_solve_kernel<<<n_jobs, JOB_THREADS, 0, st>>>(J, dP.as<float>(), dQ.as<float>(), dkeys.as<unsigned long long>(), actv + it);
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             icp_move_kernel<<<gp, PT_THREADS, 0, st>>>(J, dP.as<float>(), dM.as<float4>());
-            ICP_STEP(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             if ((it + 1) % check_every == 0 && it + 1 < max_it[li]) {       // every job done: stop queueing the level
-                ICP_STEP(hipMemcpyAsync(act.data(), actv + it, sizeof(int), hipMemcpyDeviceToHost, st));
-                ICP_STEP(hipStreamSynchronize(st));
+                HIP_TRY(hipMemcpyAsync(act.data(), actv + it, sizeof(int), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
                 if (act[0] == 0) break;
             }
         }
         icp_level_end_kernel<<<jb, 64, 0, st>>>(J, n_jobs);
-        ICP_STEP(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     icp_finish_kernel<<<jb, 64, 0, st>>>(J, n_jobs);
-    ICP_STEP(hipGetLastError());
-    ICP_STEP(hipMemcpyAsync(hj.data(), J, sizeof(IcpJob) * n_jobs, hipMemcpyDeviceToHost, st));
-    ICP_STEP(hipStreamSynchronize(st));
-#undef ICP_STEP
-    cleanup();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(hj.data(), J, sizeof(IcpJob) * n_jobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int j = 0; j < n_jobs; ++j) {
         const IcpJob& H = hj[j];
         p2p_icp_result& R = out[j];
@@ -852,19 +826,14 @@ int refine_chain(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, i
     if ((rc = icp_check(who, params, nullptr, 0, P))) return rc;
     std::vector<p2p_icp_input> in(std::max(n_jobs, 1));
     IcpInputsStage S;
-    rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, in.data(), S, dev_inputs);
-    if (rc == P2P_OK && n_jobs > 0) rc = icp_check(who, params, in.data(), n_jobs, P);
-    if (rc || n_jobs == 0) {
-        S.release();
+    if ((rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, in.data(), S, dev_inputs)))
         return rc;
-    }
+    if (n_jobs == 0) return P2P_OK;
+    if ((rc = icp_check(who, params, in.data(), n_jobs, P))) return rc;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
     hipStream_t st = c->stream;
     std::vector<p2p_icp_result> icp(n_jobs);
-    if ((rc = icp_run(*c, in.data(), n_jobs, S.dsrc.as<float>(), S.dtgt.as<float>(), P, icp.data()))) {
-        S.release();
-        return rc;
-    }
+    if ((rc = icp_run(*c, in.data(), n_jobs, S.dsrc.as<float>(), S.dtgt.as<float>(), P, icp.data()))) return rc;
     // tf = pose * [R | t_adjusted / 1000] (icp_refinement :91-93), R_ref = tf[:3,:3], t_ref = tf[:3,3] * 1000 (:466-467)
     std::vector<p2p_refine_job> rj(jobs, jobs + n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
@@ -898,30 +867,19 @@ int refine_chain(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, i
     // the score at the refined pose (the frames and union masks of the stage; every job is scored, the gated ones are zeroed below)
     const size_t HW = (size_t)height * width;
     DevBuf dof, dout, dz, dj;
-    auto cleanup = [&]() { S.release(); dof.release(); dout.release(); dz.release(); dj.release(); };
     if ((rc = dof.reserve(sizeof(int) * n_jobs)) || (rc = dout.reserve(sizeof(p2p_depth_score) * n_jobs)) ||
-        (dinl_alloc && (rc = dinl_alloc->reserve(n_jobs * HW)))) {
-        cleanup();
+        (dinl_alloc && (rc = dinl_alloc->reserve(n_jobs * HW))))
         return rc;
-    }
     if (dinl_alloc) dinl = dinl_alloc->as<unsigned char>();
     std::vector<p2p_depth_score> sc(n_jobs);
-    hipError_t e = hipMemcpyAsync(dof.p, S.slot_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess &&
-        (rc = score_into(*c, meshes, rj.data(), n_jobs, height, width, S.dimg.as<float>(), dof.as<int>(), S.dumask.as<unsigned char>(),
-                         dinl, dout.as<p2p_depth_score>(), dz, dj))) {
-        cleanup();
+    HIP_TRY(hipMemcpyAsync(dof.p, S.slot_of.data(), sizeof(int) * n_jobs, hipMemcpyHostToDevice, st));
+    if ((rc = score_into(*c, meshes, rj.data(), n_jobs, height, width, S.dimg.as<float>(), dof.as<int>(), S.dumask.as<unsigned char>(),
+                         dinl, dout.as<p2p_depth_score>(), dz, dj)))
         return rc;
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(sc.data(), dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st);
-    for (int j = 0; j < n_jobs && e == hipSuccess && dinl; ++j)
-        if (icp[j].status != 0) e = hipMemsetAsync(dinl + j * HW, 0, HW, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    }
+    HIP_TRY(hipMemcpyAsync(sc.data(), dout.p, sizeof(p2p_depth_score) * n_jobs, hipMemcpyDeviceToHost, st));
+    for (int j = 0; j < n_jobs && dinl; ++j)
+        if (icp[j].status != 0) HIP_TRY(hipMemsetAsync(dinl + j * HW, 0, HW, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int j = 0; j < n_jobs; ++j)
         if (icp[j].status == 0) out[j].score = sc[j];
     return P2P_OK;
@@ -957,23 +915,12 @@ int p2p_icp_batch(p2p_ctx* ctx, const p2p_icp_input* inputs, int n_jobs, const f
     }
     if (n_jobs == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ICP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     DevBuf ds, dt;
-    hipError_t e = hipSuccess;
-    if ((rc = ds.reserve(std::max<int64_t>(ns, 1) * 24)) || (rc = dt.reserve(std::max<int64_t>(nt, 1) * 24))) {
-        ds.release(); dt.release();
-        return rc;
-    }
-    if (ns > 0) e = hipMemcpyAsync(ds.p, src_points, ns * 24, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nt > 0) e = hipMemcpyAsync(dt.p, tgt_points, nt * 24, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        ds.release(); dt.release();
-        return P2P_ERR_HIP;
-    }
-    rc = icp_run(*c, inputs, n_jobs, ds.as<float>(), dt.as<float>(), P, out);
-    ds.release(); dt.release();
-    return rc;
+    if ((rc = ds.reserve(std::max<int64_t>(ns, 1) * 24)) || (rc = dt.reserve(std::max<int64_t>(nt, 1) * 24))) return rc;
+    if (ns > 0) HIP_TRY(hipMemcpyAsync(ds.p, src_points, ns * 24, hipMemcpyHostToDevice, c->stream));
+    if (nt > 0) HIP_TRY(hipMemcpyAsync(dt.p, tgt_points, nt * 24, hipMemcpyHostToDevice, c->stream));
+    return icp_run(*c, inputs, n_jobs, ds.as<float>(), dt.as<float>(), P, out);
 }
 
 int p2p_refine_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images, int n_images,
@@ -984,17 +931,11 @@ int p2p_refine_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_me
     DevBuf dinl;       // the inlier masks on the device, allocated by the chain once its checks have passed
     int rc = refine_chain(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, params, out, nullptr, false,
                           inlier_masks ? &dinl : nullptr);
-    if (rc == P2P_OK && inlier_masks && n_jobs > 0) {
-        hipStream_t st = reinterpret_cast<Ctx*>(ctx)->stream;
-        hipError_t e = hipMemcpyAsync(inlier_masks, dinl.p, (size_t)n_jobs * height * width, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error("%s: %s", who, hipGetErrorString(e));
-            rc = P2P_ERR_HIP;
-        }
-    }
-    dinl.release();
-    return rc;
+    if (rc || !inlier_masks || n_jobs == 0) return rc;
+    hipStream_t st = reinterpret_cast<Ctx*>(ctx)->stream;
+    HIP_TRY(hipMemcpyAsync(inlier_masks, dinl.p, (size_t)n_jobs * height * width, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return P2P_OK;
 }
 
 }  // extern "C"

@@ -15,6 +15,16 @@ namespace p2p {
 void set_error(const char* fmt, ...);
 const char* get_error();
 
+// Evaluates a HIP runtime call; on failure records "<expr> failed: <error> (<file>:<line>)" and returns P2P_ERR_HIP.
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess) {                                                               \
+            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return P2P_ERR_HIP;                                                               \
+        }                                                                                     \
+    } while (0)
+
 // One packed dense contraction (device pointers).
 struct ConvLayer {
     float* w = nullptr;       // [Cout_pad][K]  (conv_first: [K][Cout])

@@ -27,15 +27,6 @@ void set_error(const char* fmt, ...)
 }
 const char* get_error() { return g_err; }
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 constexpr double BN_EPS = 1e-3;     // Keras BatchNormalization default
 constexpr float LEAKY = 0.3f;       // keras.layers.LeakyReLU() default
 

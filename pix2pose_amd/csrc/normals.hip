@@ -23,15 +23,6 @@ namespace p2p {
 
 namespace {
 
-#define NRM_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 constexpr int FILL_LAYERS = 10;                   // L of the onion-peel fill; outputs at d > 0 do not depend on it once L >= 10
 constexpr int GAUSS_R = 8;                        // ndimage.gaussian_filter(., 2): truncate 4.0 -> radius 8
 constexpr int NRM_GROW = GAUSS_R + 2 * FILL_LAYERS;   // crop -> work region of a job (a filled value reads 2 px per layer)
@@ -348,18 +339,18 @@ int run_items(hipStream_t st, const std::vector<NrmItem>& items, const NrmItem* 
     const unsigned n = (unsigned)items.size();
     const dim3 blk(TX, TY), gr((mrw + TX - 1) / TX, (mrh + TY - 1) / TY, n), gc((mgw + TX - 1) / TX, (mgh + TY - 1) / TY, n);
     fill_init_kernel<<<gr, blk, 0, st>>>(ditems, W);
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     for (int k = 0; k < FILL_LAYERS; ++k) {
         fill_layer_kernel<<<gr, blk, 0, st>>>(ditems, k & 1);
-        NRM_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     const GaussW g = gauss_weights();
     gauss_kernel<0><<<gr, blk, 0, st>>>(ditems, H, W, g, FILL_LAYERS & 1);
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     gauss_kernel<1><<<gr, blk, 0, st>>>(ditems, H, W, g, FILL_LAYERS & 1);
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     normal_kernel<<<gc, blk, 0, st>>>(ditems, W);
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return P2P_OK;
 }
 
@@ -433,9 +424,9 @@ int frame_points(hipStream_t st, const float* const* depth_images, const int* im
     }
     if ((rc = alloc_items(items, dwork, false)) || (rc = ditems.reserve(sizeof(NrmItem) * n))) return rc;
     for (int f = 0; f < n; ++f)
-        NRM_TRY(hipMemcpyAsync(dimg.as<float>() + f * HW, depth_images[img[f]], HW * 4,
+        HIP_TRY(hipMemcpyAsync(dimg.as<float>() + f * HW, depth_images[img[f]], HW * 4,
                                dev_inputs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-    NRM_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(NrmItem) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(NrmItem) * n, hipMemcpyHostToDevice, st));
     return run_items(st, items, ditems.as<NrmItem>(), H, W);
 }
 
@@ -448,13 +439,13 @@ int compact_count(hipStream_t st, std::vector<CmpItem>& items, DevBuf& ditems, D
     for (CmpItem& I : items) { I.row_base = rows; rows += I.rows; max_rows = std::max(max_rows, I.rows); }
     int rc;
     if ((rc = ditems.reserve(sizeof(CmpItem) * n)) || (rc = drow.reserve(sizeof(int64_t) * std::max<int64_t>(rows, 1)))) return rc;
-    NRM_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(CmpItem) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(CmpItem) * n, hipMemcpyHostToDevice, st));
     cmp_count_kernel<<<dim3(max_rows, n), 64, 0, st>>>(ditems.as<CmpItem>(), drow.as<int64_t>());
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     cmp_scan_kernel<<<(n + 63) / 64, 64, 0, st>>>(ditems.as<CmpItem>(), n, drow.as<int64_t>());
-    NRM_TRY(hipGetLastError());
-    NRM_TRY(hipMemcpyAsync(items.data(), ditems.p, sizeof(CmpItem) * n, hipMemcpyDeviceToHost, st));
-    NRM_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(items.data(), ditems.p, sizeof(CmpItem) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 
@@ -463,9 +454,9 @@ int compact_write(hipStream_t st, const std::vector<CmpItem>& items, DevBuf& dit
 {
     int max_rows = 1;
     for (const CmpItem& I : items) max_rows = std::max(max_rows, I.rows);
-    NRM_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(CmpItem) * items.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ditems.p, items.data(), sizeof(CmpItem) * items.size(), hipMemcpyHostToDevice, st));
     cmp_write_kernel<<<dim3(max_rows, (unsigned)items.size()), 64, 0, st>>>(ditems.as<CmpItem>(), drow.as<int64_t>());
-    NRM_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return P2P_OK;
 }
 
@@ -495,36 +486,22 @@ int p2p_depth_points_batch(p2p_ctx* ctx, const float* const* depth_images, int n
     }
     if (n_images == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    NRM_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t HW = (size_t)height * width;
     DevBuf dimg, dpts, dwork, ditems;
     std::vector<int> img(n_images);
     std::vector<const double*> cams(n_images);
     for (int i = 0; i < n_images; ++i) { img[i] = i; cams[i] = camK + 9 * i; }
-    rc = frame_points(st, depth_images, img.data(), cams.data(), n_images, height, width, dimg, dpts, dwork, ditems);
-    hipError_t e = hipSuccess;
-    if (rc == P2P_OK && (e = hipMemcpyAsync(points, dpts.p, n_images * HW * 24, hipMemcpyDeviceToHost, st)) == hipSuccess)
-        e = hipStreamSynchronize(st);
-    for (DevBuf* b : {&dimg, &dpts, &dwork, &ditems}) b->release();
-    if (rc) return rc;
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    }
+    if ((rc = frame_points(st, depth_images, img.data(), cams.data(), n_images, height, width, dimg, dpts, dwork, ditems))) return rc;
+    HIP_TRY(hipMemcpyAsync(points, dpts.p, n_images * HW * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 
 }  // extern "C"
 
 namespace p2p {
-
-void IcpInputsStage::release()
-{
-    for (DevBuf* b : {&dimg, &dumask, &dscene, &dwork, &ditems, &dcmp, &drow, &dcmp2, &drow2, &dtgt, &dsrc, &dz, &dj, &dbox, &dctgt,
-                      &dcsrc, &djob_of, &dwork2, &ditems2})
-        b->release();
-}
 
 int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
                      int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S,
@@ -546,29 +523,13 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
         }
     if (n_jobs == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    NRM_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t HW = (size_t)height * width;
     const bool whole = dev_env("P2P_NORMALS_WHOLE") != nullptr;     // development twin: jobs' fill and Gaussian over the whole frame
 
-    // (every buffer has one use: DevBuf::reserve frees, so a buffer read by queued work is never grown)
-    DevBuf &dimg = S.dimg, &dumask = S.dumask, &dscene = S.dscene, &dwork = S.dwork, &ditems = S.ditems, &dcmp = S.dcmp, &drow = S.drow,
-           &dcmp2 = S.dcmp2, &drow2 = S.drow2, &dtgt = S.dtgt, &dsrc = S.dsrc, &dz = S.dz, &dj = S.dj, &dbox = S.dbox, &dctgt = S.dctgt,
-           &dcsrc = S.dcsrc, &djob_of = S.djob_of, &dwork2 = S.dwork2, &ditems2 = S.ditems2;
-    auto cleanup = [&]() { S.release(); };
-#define NRM_STEP(expr)              \
-    do {                            \
-        if ((rc = (expr))) {        \
-            cleanup();              \
-            return rc;              \
-        }                           \
-    } while (0)
-    auto hip = [&](hipError_t e) -> int {
-        if (e == hipSuccess) return P2P_OK;
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    };
-
+    // the buffers are S's and live until the caller's stage goes out of scope; each has one use (DevBuf::reserve frees before it grows,
+    // so a buffer read by queued work is never reserved again)
     // 1. the sensor frames the jobs name and the union masks; scene points of each frame once per camera it is seen with (the reference
     //    computes points_tgt once per image with that image's cam_K, icp3d.py:372-374)
     std::vector<int> frames, frame_job, slot_of(n_jobs);      // frame -> image, first job naming it; job -> frame
@@ -586,34 +547,36 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
     const int nf = (int)frames.size();
     std::vector<const double*> cams(nf);
     for (int f = 0; f < nf; ++f) cams[f] = jobs[frame_job[f]].camK;
-    NRM_STEP(frame_points(st, depth_images, frames.data(), cams.data(), nf, height, width, dimg, dscene, dwork, ditems, dev_inputs));
-    NRM_STEP(dumask.reserve(n_jobs * HW));
+    if ((rc = frame_points(st, depth_images, frames.data(), cams.data(), nf, height, width, S.dimg, S.dscene, S.dwork, S.ditems,
+                           dev_inputs)))
+        return rc;
+    if ((rc = S.dumask.reserve(n_jobs * HW))) return rc;
     for (int j = 0; j < n_jobs; ++j)
-        NRM_STEP(hip(hipMemcpyAsync(dumask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW,
-                                    dev_inputs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st)));
+        HIP_TRY(hipMemcpyAsync(S.dumask.as<unsigned char>() + j * HW, jobs[j].union_mask, HW,
+                               dev_inputs ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
 
     // 2. target points pts_tgt = points_tgt[union_mask] (:464) and their centroid (icp_refinement :59)
     std::vector<CmpItem> titems(n_jobs);
     for (int j = 0; j < n_jobs; ++j) {
         CmpItem& T = titems[j];
         T = CmpItem{};
-        T.pts = dscene.as<float>() + slot_of[j] * HW * 6;
-        T.mask = dumask.as<unsigned char>() + j * HW;
+        T.pts = S.dscene.as<float>() + slot_of[j] * HW * 6;
+        T.mask = S.dumask.as<unsigned char>() + j * HW;
         T.rows = height; T.cols = width;
     }
-    NRM_STEP(compact_count(st, titems, dcmp, drow));
+    if ((rc = compact_count(st, titems, S.dcmp, S.drow))) return rc;
     int64_t tot_tgt = 0;
     std::vector<int64_t> tgt_off(n_jobs);
     for (int j = 0; j < n_jobs; ++j) { tgt_off[j] = tot_tgt; tot_tgt += titems[j].n; }
-    NRM_STEP(dtgt.reserve(std::max<int64_t>(tot_tgt, 1) * 24));
-    for (int j = 0; j < n_jobs; ++j) titems[j].out = dtgt.as<float>() + tgt_off[j] * 6;
-    NRM_STEP(compact_write(st, titems, dcmp, drow));
-    NRM_STEP(dctgt.reserve(sizeof(double) * 3 * n_jobs));
-    centroid_kernel<<<n_jobs, CENT_THREADS, 0, st>>>(dcmp.as<CmpItem>(), dctgt.as<double>());
-    NRM_STEP(hip(hipGetLastError()));
+    if ((rc = S.dtgt.reserve(std::max<int64_t>(tot_tgt, 1) * 24))) return rc;
+    for (int j = 0; j < n_jobs; ++j) titems[j].out = S.dtgt.as<float>() + tgt_off[j] * 6;
+    if ((rc = compact_write(st, titems, S.dcmp, S.drow))) return rc;
+    if ((rc = S.dctgt.reserve(sizeof(double) * 3 * n_jobs))) return rc;
+    centroid_kernel<<<n_jobs, CENT_THREADS, 0, st>>>(S.dcmp.as<CmpItem>(), S.dctgt.as<double>());
+    HIP_TRY(hipGetLastError());
     std::vector<double> ctgt(3 * n_jobs);
-    NRM_STEP(hip(hipMemcpyAsync(ctgt.data(), dctgt.p, sizeof(double) * 3 * n_jobs, hipMemcpyDeviceToHost, st)));
-    NRM_STEP(hip(hipStreamSynchronize(st)));
+    HIP_TRY(hipMemcpyAsync(ctgt.data(), S.dctgt.p, sizeof(double) * 3 * n_jobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
 
     // 3. t replacement (:60-61) and the render at that pose (:64-67)
     std::vector<p2p_refine_job> rj(jobs, jobs + n_jobs);
@@ -626,16 +589,16 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
         const bool replace = jobs[j].t[2] < 300.0 || jobs[j].t[2] > 5000.0;
         for (int q = 0; q < 3; ++q) R.t_init[q] = rj[j].t[q] = replace ? ctgt[3 * j + q] * 1000.0 : jobs[j].t[q];
     }
-    NRM_STEP(dz.reserve(n_jobs * HW * 4));
-    NRM_STEP(render_into(*c, meshes, rj.data(), n_jobs, height, width, dz.as<unsigned>(), dj));
+    if ((rc = S.dz.reserve(n_jobs * HW * 4))) return rc;
+    if ((rc = render_into(*c, meshes, rj.data(), n_jobs, height, width, S.dz.as<unsigned>(), S.dj))) return rc;
 
     // 4. init_mask, its bbox and the two gates (:68-74)
-    NRM_STEP(dbox.reserve(sizeof(int) * 5 * n_jobs));
-    init_box_kernel<<<n_jobs, BOX_THREADS, 0, st>>>(dz.as<float>(), dumask.as<unsigned char>(), height, width, dbox.as<int>());
-    NRM_STEP(hip(hipGetLastError()));
+    if ((rc = S.dbox.reserve(sizeof(int) * 5 * n_jobs))) return rc;
+    init_box_kernel<<<n_jobs, BOX_THREADS, 0, st>>>(S.dz.as<float>(), S.dumask.as<unsigned char>(), height, width, S.dbox.as<int>());
+    HIP_TRY(hipGetLastError());
     std::vector<int> box(5 * n_jobs);
-    NRM_STEP(hip(hipMemcpyAsync(box.data(), dbox.p, sizeof(int) * 5 * n_jobs, hipMemcpyDeviceToHost, st)));
-    NRM_STEP(hip(hipStreamSynchronize(st)));
+    HIP_TRY(hipMemcpyAsync(box.data(), S.dbox.p, sizeof(int) * 5 * n_jobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     std::vector<NrmItem> sitems;
     std::vector<int> job_of;
     for (int j = 0; j < n_jobs; ++j) {
@@ -649,8 +612,8 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
             R.status = P2P_ICP_FEW_POINTS;
         if (R.status != P2P_ICP_OK) continue;
         // points_src over [rmin, rmax) x [cmin, cmax): the inclusive max of get_bbox_from_mask used as an exclusive slice end
-        NrmItem I = frame_item(dz.as<float>() + j * HW, jobs[j].camK, height, width);
-        I.umask = dumask.as<unsigned char>() + j * HW;
+        NrmItem I = frame_item(S.dz.as<float>() + j * HW, jobs[j].camK, height, width);
+        I.umask = S.dumask.as<unsigned char>() + j * HW;
         I.g0 = R.bbox[0]; I.gc0 = R.bbox[1]; I.gh = R.bbox[2] - R.bbox[0]; I.gw = R.bbox[3] - R.bbox[1];
         if (!whole) {
             I.r0 = std::max(0, I.g0 - NRM_GROW); I.c0 = std::max(0, I.gc0 - NRM_GROW);
@@ -664,17 +627,17 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
     const int ns = (int)sitems.size();
     std::vector<CmpItem> citems(ns);
     if (ns > 0) {
-        NRM_STEP(alloc_items(sitems, dwork2, true));
-        NRM_STEP(ditems2.reserve(sizeof(NrmItem) * ns));
-        NRM_STEP(hip(hipMemcpyAsync(ditems2.p, sitems.data(), sizeof(NrmItem) * ns, hipMemcpyHostToDevice, st)));
-        NRM_STEP(run_items(st, sitems, ditems2.as<NrmItem>(), height, width));
+        if ((rc = alloc_items(sitems, S.dwork2, true))) return rc;
+        if ((rc = S.ditems2.reserve(sizeof(NrmItem) * ns))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.ditems2.p, sitems.data(), sizeof(NrmItem) * ns, hipMemcpyHostToDevice, st));
+        if ((rc = run_items(st, sitems, S.ditems2.as<NrmItem>(), height, width))) return rc;
         for (int k = 0; k < ns; ++k) {
             citems[k] = CmpItem{};
             citems[k].pts = sitems[k].pts;
             citems[k].mask = sitems[k].cmask;
             citems[k].rows = sitems[k].gh; citems[k].cols = sitems[k].gw;
         }
-        NRM_STEP(compact_count(st, citems, dcmp2, drow2));
+        if ((rc = compact_count(st, citems, S.dcmp2, S.drow2))) return rc;
     }
     int64_t tot_src = 0;
     for (int j = 0, k = 0; j < n_jobs; ++j) {      // packed in job order; a gated job has no source points and keeps t = t_init
@@ -687,22 +650,22 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
         }
     }
     if (ns > 0) {
-        NRM_STEP(dsrc.reserve(std::max<int64_t>(tot_src, 1) * 24));
-        for (int k = 0; k < ns; ++k) citems[k].out = dsrc.as<float>() + out[job_of[k]].src_offset * 6;
-        NRM_STEP(compact_write(st, citems, dcmp2, drow2));
-        NRM_STEP(dcsrc.reserve(sizeof(double) * 3 * ns));
-        NRM_STEP(djob_of.reserve(sizeof(int) * ns));
-        NRM_STEP(hip(hipMemcpyAsync(djob_of.p, job_of.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st)));
-        centroid_kernel<<<ns, CENT_THREADS, 0, st>>>(dcmp2.as<CmpItem>(), dcsrc.as<double>());
-        NRM_STEP(hip(hipGetLastError()));
+        if ((rc = S.dsrc.reserve(std::max<int64_t>(tot_src, 1) * 24))) return rc;
+        for (int k = 0; k < ns; ++k) citems[k].out = S.dsrc.as<float>() + out[job_of[k]].src_offset * 6;
+        if ((rc = compact_write(st, citems, S.dcmp2, S.drow2))) return rc;
+        if ((rc = S.dcsrc.reserve(sizeof(double) * 3 * ns))) return rc;
+        if ((rc = S.djob_of.reserve(sizeof(int) * ns))) return rc;
+        HIP_TRY(hipMemcpyAsync(S.djob_of.p, job_of.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
+        centroid_kernel<<<ns, CENT_THREADS, 0, st>>>(S.dcmp2.as<CmpItem>(), S.dcsrc.as<double>());
+        HIP_TRY(hipGetLastError());
         int64_t maxn = 1;
         for (int k = 0; k < ns; ++k) maxn = std::max(maxn, citems[k].n);
-        shift_kernel<<<dim3((unsigned)((maxn + 255) / 256), ns), 256, 0, st>>>(dcmp2.as<CmpItem>(), djob_of.as<int>(), dctgt.as<double>(),
-                                                                             dcsrc.as<double>());
-        NRM_STEP(hip(hipGetLastError()));
+        shift_kernel<<<dim3((unsigned)((maxn + 255) / 256), ns), 256, 0, st>>>(S.dcmp2.as<CmpItem>(), S.djob_of.as<int>(),
+                                                                             S.dctgt.as<double>(), S.dcsrc.as<double>());
+        HIP_TRY(hipGetLastError());
         std::vector<double> csrc(3 * ns);
-        NRM_STEP(hip(hipMemcpyAsync(csrc.data(), dcsrc.p, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, st)));
-        NRM_STEP(hip(hipStreamSynchronize(st)));
+        HIP_TRY(hipMemcpyAsync(csrc.data(), S.dcsrc.p, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < ns; ++k) {
             p2p_icp_input& R = out[job_of[k]];
             for (int q = 0; q < 3; ++q) {
@@ -715,7 +678,6 @@ int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshe
     S.slot_of = slot_of;
     S.tot_src = tot_src;
     S.tot_tgt = tot_tgt;
-#undef NRM_STEP
     return P2P_OK;
 }
 
@@ -734,28 +696,18 @@ int p2p_icp_inputs_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_mesh
     }
     IcpInputsStage S;
     int rc = icp_inputs_stage(who, ctx, meshes, n_meshes, depth_images, n_images, jobs, n_jobs, height, width, out, S);
-    if (rc || n_jobs == 0) {
-        S.release();
-        return rc;
-    }
+    if (rc || n_jobs == 0) return rc;
     hipStream_t st = reinterpret_cast<Ctx*>(ctx)->stream;
 
     // the point buffers, if they are given and large enough
     if ((src_points && S.tot_src > src_capacity) || (tgt_points && S.tot_tgt > tgt_capacity)) {
         set_error("%s: %lld source / %lld target points, capacities %lld / %lld", who, (long long)S.tot_src, (long long)S.tot_tgt,
                   (long long)src_capacity, (long long)tgt_capacity);
-        S.release();
         return P2P_ERR_CAPACITY;
     }
-    hipError_t e = hipSuccess;
-    if (src_points && S.tot_src > 0) e = hipMemcpyAsync(src_points, S.dsrc.p, S.tot_src * 24, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && tgt_points && S.tot_tgt > 0) e = hipMemcpyAsync(tgt_points, S.dtgt.p, S.tot_tgt * 24, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    S.release();
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    }
+    if (src_points && S.tot_src > 0) HIP_TRY(hipMemcpyAsync(src_points, S.dsrc.p, S.tot_src * 24, hipMemcpyDeviceToHost, st));
+    if (tgt_points && S.tot_tgt > 0) HIP_TRY(hipMemcpyAsync(tgt_points, S.dtgt.p, S.tot_tgt * 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 

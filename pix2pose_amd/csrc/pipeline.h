@@ -116,20 +116,33 @@ hipError_t launch_pnp_ransac(const PnpProblem* probs, PnpResult* results, int n_
                              double reproj_err, double confidence, int min_points, int max_points, double* workspace, hipStream_t s);
 // max_points: upper bound of PnpProblem::n over the problems (shapes the counting launch; results do not depend on it)
 
-// growable device buffer
+// growable device buffer that owns its memory: freed by the destructor (hipFree waits for the device), or earlier by release().
+// reserve() frees before it allocates, so a buffer read by queued work is never grown.  Movable, not copyable.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept;
+    ~DevBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
 // growable pinned host buffer (D2H landing zone: the copy is truly asynchronous and the caller's pageable
-// buffer is filled with one memcpy at collect time)
+// buffer is filled with one memcpy at collect time); owns its memory like DevBuf
 struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept;
+    ~PinnedBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
@@ -216,13 +229,12 @@ int score_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs
 
 // The ICP inputs of p2p_icp_inputs_batch (normals.hip) left on the device: argument checks, records `out`, and the packed source /
 // target points (dsrc / dtgt, tot_src / tot_tgt points of 6 float32), the sensor frames dimg [slot][H][W] (slot_of[j]: job j's frame)
-// and the union masks dumask [n_jobs][H][W].  The caller releases the stage on every return.  dev_inputs: depth_images and the jobs'
-// union_mask pointers are device memory (rgbd.hip), copied on the device; otherwise host memory.
+// and the union masks dumask [n_jobs][H][W].  The stage's buffers live as long as the caller's IcpInputsStage.  dev_inputs: depth_images
+// and the jobs' union_mask pointers are device memory (rgbd.hip), copied on the device; otherwise host memory.
 struct IcpInputsStage {
     DevBuf dimg, dumask, dscene, dwork, ditems, dcmp, drow, dcmp2, drow2, dtgt, dsrc, dz, dj, dbox, dctgt, dcsrc, djob_of, dwork2, ditems2;
     std::vector<int> slot_of;
     int64_t tot_src = 0, tot_tgt = 0;
-    void release();
 };
 int icp_inputs_stage(const char* who, p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const float* const* depth_images,
                      int n_images, const p2p_refine_job* jobs, int n_jobs, int height, int width, p2p_icp_input* out, IcpInputsStage& S,

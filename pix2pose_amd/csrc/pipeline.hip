@@ -20,15 +20,6 @@
 
 namespace p2p {
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
-
 int DevBuf::reserve(size_t bytes)
 {
     if (bytes <= cap) return P2P_OK;
@@ -48,6 +39,15 @@ void DevBuf::release()
     if (p) (void)hipFree(p);
     p = nullptr;
     cap = 0;
+}
+DevBuf& DevBuf::operator=(DevBuf&& o) noexcept
+{
+    if (this != &o) {
+        release();
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+    return *this;
 }
 int PinnedBuf::reserve(size_t bytes)
 {
@@ -69,12 +69,18 @@ void PinnedBuf::release()
     p = nullptr;
     cap = 0;
 }
-Pipeline::~Pipeline()
+PinnedBuf& PinnedBuf::operator=(PinnedBuf&& o) noexcept
+{
+    if (this != &o) {
+        release();
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
+    return *this;
+}
+Pipeline::~Pipeline()      // the slots' DevBuf / PinnedBuf members free themselves after this body
 {
     for (Slot& s : slot) {
-        for (DevBuf* b : {&s.det, &s.s1, &s.cand, &s.probs, &s.results, &s.poses, &s.corr, &s.hyp, &s.x1, &s.y1, &s.x2, &s.y2, &s.images, &s.crec, &s.cseg, &s.sacc,
-                          &s.mask, &s.pred, &s.dmask, &s.mstat, &s.crange, &s.aa_items, &s.aa_cv, &s.aa_cv_tmp, &s.aa_bk, &s.aa_bk_tmp, &s.keepf}) b->release();
-        for (PinnedBuf* b : {&s.h_mask, &s.h_pred, &s.h_stat, &s.h_frames, &s.h_range}) b->release();
         if (s.host_poses) (void)hipHostFree(s.host_poses);
         if (s.done) (void)hipEventDestroy(s.done);
     }
@@ -1957,21 +1963,20 @@ int p2p_debug_back_resize(p2p_ctx* ctx, const float* prob, const float* pred, co
     DevBuf planes, tmp, items, dq, db, dg;
     int rc;
     const size_t npx = (size_t)out_h * out_w;
-    auto cleanup = [&]() { planes.release(); tmp.release(); items.release(); dq.release(); db.release(); dg.release(); };
     if ((rc = planes.reserve(h.size() * 8)) || (rc = tmp.reserve(h.size() * 8)) || (rc = items.reserve(5 * sizeof(AaItem))) ||
-        (rc = dq.reserve(npx * 3)) || (rc = db.reserve(npx)) || (rc = dg.reserve(npx))) { cleanup(); return rc; }
-    hipError_t e = hipMemcpyAsync(planes.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, st);
+        (rc = dq.reserve(npx * 3)) || (rc = db.reserve(npx)) || (rc = dg.reserve(npx))) return rc;
+    HIP_TRY(hipMemcpyAsync(planes.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, st));
     CandRange R;
     R.pmin = lo[0]; R.pmax = hi[0];
     R.qmin = std::min(lo[1], std::min(lo[2], lo[3])); R.qmax = std::max(hi[1], std::max(hi[2], hi[3]));
     R.gmin = lo[4]; R.gmax = hi[4];
-    if (e == hipSuccess && generation && out_h < 128) {          // scikit-image 0.17 / 0.18: anti-aliasing filter before a shrinking resize (square outputs, like the path's)
+    if (generation && out_h < 128) {          // scikit-image 0.17 / 0.18: anti-aliasing filter before a shrinking resize (square outputs, like the path's)
         AaTable tab;
-        if ((rc = aa_table_get(c->device, &tab))) { cleanup(); return rc; }
+        if ((rc = aa_table_get(c->device, &tab))) return rc;
         std::vector<int> rad(tab.max_side + 1), off(tab.max_side + 1);
-        e = hipMemcpy(rad.data(), tab.rad, rad.size() * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(off.data(), tab.off, off.size() * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rad[out_h] > 0) {
+        HIP_TRY(hipMemcpy(rad.data(), tab.rad, rad.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(off.data(), tab.off, off.size() * 4, hipMemcpyDeviceToHost));
+        if (rad[out_h] > 0) {
             AaItem it[5];
             for (int k = 0; k < 5; ++k) {
                 memset(&it[k], 0, sizeof(AaItem));
@@ -1979,28 +1984,22 @@ int p2p_debug_back_resize(p2p_ctx* ctx, const float* prob, const float* pred, co
                 it[k].H = it[k].W = 128; it[k].C = 1; it[k].radius = rad[out_h]; it[k].w = tab.w + off[out_h];
                 it[k].mode = 1; it[k].cval = k == 0 ? 1.0 : (k == 4 ? 0.0 : 0.5); it[k].round32 = k < 4;
             }
-            e = hipMemcpyAsync(items.p, it, sizeof(it), hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = launch_aa_filter(items.as<AaItem>(), 5, 16384, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(it, items.p, sizeof(it), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e == hipSuccess) {
-                R.pmin = it[0].vmin; R.pmax = it[0].vmax;
-                R.qmin = std::min(it[1].vmin, std::min(it[2].vmin, it[3].vmin)); R.qmax = std::max(it[1].vmax, std::max(it[2].vmax, it[3].vmax));
-                R.gmin = it[4].vmin; R.gmax = it[4].vmax;
-            }
+            HIP_TRY(hipMemcpyAsync(items.p, it, sizeof(it), hipMemcpyHostToDevice, st));
+            HIP_TRY(launch_aa_filter(items.as<AaItem>(), 5, 16384, st));
+            HIP_TRY(hipMemcpyAsync(it, items.p, sizeof(it), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            R.pmin = it[0].vmin; R.pmax = it[0].vmax;
+            R.qmin = std::min(it[1].vmin, std::min(it[2].vmin, it[3].vmin)); R.qmax = std::max(it[1].vmax, std::max(it[2].vmax, it[3].vmax));
+            R.gmin = it[4].vmin; R.gmax = it[4].vmax;
         }
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(back_resize_probe_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, planes.as<double>(), R, out_h, out_w, th_inlier,
-                           generation == 1 ? 1 : 0, dq.as<unsigned char>(), db.as<unsigned char>(), dg.as<unsigned char>());
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(q, dq.p, npx * 3, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(below, db.p, npx, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ng_out, dg.p, npx, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
-    if (e != hipSuccess) { set_error("p2p_debug_back_resize: %s", hipGetErrorString(e)); return P2P_ERR_HIP; }
+    hipLaunchKernelGGL(back_resize_probe_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, planes.as<double>(), R, out_h, out_w, th_inlier,
+                       generation == 1 ? 1 : 0, dq.as<unsigned char>(), db.as<unsigned char>(), dg.as<unsigned char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(q, dq.p, npx * 3, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(below, db.p, npx, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ng_out, dg.p, npx, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 
@@ -2046,10 +2045,8 @@ int p2p_pnp_ransac_batch(p2p_ctx* ctx, const double* camK, const double* obj_pts
     int rc;
     if ((rc = dpts.reserve(pts.size() * 4)) || (rc = dprob.reserve(sizeof(PnpProblem) * n_problems)) ||
         (rc = dres.reserve(sizeof(PnpResult) * n_problems)) || (rc = dmask.reserve((size_t)std::max(N, 1))) ||
-        (rc = dhyp.reserve(pnp_workspace_bytes(n_problems)))) {
-        dpts.release(); dprob.release(); dres.release(); dmask.release(); dhyp.release();
+        (rc = dhyp.reserve(pnp_workspace_bytes(n_problems))))
         return rc;
-    }
     int max_n = 1;
     for (int p = 0; p < n_problems; ++p) {
         const int o = offsets[p], n = offsets[p + 1] - o;
@@ -2067,28 +2064,21 @@ int p2p_pnp_ransac_batch(p2p_ctx* ctx, const double* camK, const double* obj_pts
         for (int k = 0; k < 9; ++k) pb[p].K[k] = camK[9 * p + k];
         pb[p].mask = inlier_mask ? dmask.as<unsigned char>() + o : nullptr;
     }
-    auto cleanup = [&]() { dpts.release(); dprob.release(); dres.release(); dmask.release(); dhyp.release(); };
-    hipError_t e;
     std::vector<PnpResult> res(n_problems);
-    if ((e = hipMemcpyAsync(dpts.p, pts.data(), pts.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess ||
-        (e = hipMemcpyAsync(dprob.p, pb.data(), sizeof(PnpProblem) * n_problems, hipMemcpyHostToDevice, st)) != hipSuccess ||
-        (e = hipMemsetAsync(dmask.p, 0, (size_t)std::max(N, 1), st)) != hipSuccess ||
-        (e = launch_pnp_ransac(dprob.as<PnpProblem>(), dres.as<PnpResult>(), n_problems, iterations > 0 ? iterations : 100,
-                               reprojection_error > 0 ? reprojection_error : 5.0, confidence > 0 ? confidence : 0.99, 5, max_n, dhyp.as<double>(), st)) != hipSuccess ||
-        (e = hipMemcpyAsync(res.data(), dres.p, sizeof(PnpResult) * n_problems, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-        (inlier_mask && (e = hipMemcpyAsync(inlier_mask, dmask.p, (size_t)N, hipMemcpyDeviceToHost, st)) != hipSuccess) ||
-        (e = hipStreamSynchronize(st)) != hipSuccess) {
-        set_error("p2p_pnp_ransac_batch: %s", hipGetErrorString(e));
-        cleanup();
-        return P2P_ERR_HIP;
-    }
+    HIP_TRY(hipMemcpyAsync(dpts.p, pts.data(), pts.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dprob.p, pb.data(), sizeof(PnpProblem) * n_problems, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dmask.p, 0, (size_t)std::max(N, 1), st));
+    HIP_TRY(launch_pnp_ransac(dprob.as<PnpProblem>(), dres.as<PnpResult>(), n_problems, iterations > 0 ? iterations : 100,
+                              reprojection_error > 0 ? reprojection_error : 5.0, confidence > 0 ? confidence : 0.99, 5, max_n, dhyp.as<double>(), st));
+    HIP_TRY(hipMemcpyAsync(res.data(), dres.p, sizeof(PnpResult) * n_problems, hipMemcpyDeviceToHost, st));
+    if (inlier_mask) HIP_TRY(hipMemcpyAsync(inlier_mask, dmask.p, (size_t)N, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int p = 0; p < n_problems; ++p) {
         for (int k = 0; k < 9; ++k) R[9 * p + k] = res[p].R[k];
         for (int k = 0; k < 3; ++k) t[3 * p + k] = res[p].t[k];
         info[3 * p] = res[p].n_inliers; info[3 * p + 1] = res[p].iters; info[3 * p + 2] = res[p].best_iter;
         ok[p] = res[p].ok;
     }
-    cleanup();
     return P2P_OK;
 }
 

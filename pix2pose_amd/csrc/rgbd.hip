@@ -28,24 +28,9 @@ struct p2p_rgbd {
     std::vector<int> recmask_host;
     DevBuf hrec, hmask, hrecmask;                  // resolve: host-supplied records and masks
     DevBuf occ, rin, rout, err;                    // resolve: occupancy [n_images][H][W], packed inputs, rows, error flag
-    void release_all()
-    {
-        for (DevBuf* b : {&raw, &rgb, &dt, &dv, &frame, &det, &umask, &ucount, &jmeta, &inl, &rec, &recmask, &hrec, &hmask, &hrecmask, &occ,
-                          &rin, &rout, &err})
-            b->release();
-    }
 };
 
 namespace {
-
-#define RGBD_TRY(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return P2P_ERR_HIP;                                                               \
-        }                                                                                     \
-    } while (0)
 
 constexpr int PREP_THREADS = 256, UNION_THREADS = 256, RESOLVE_THREADS = 256;
 constexpr int RESOLVE_MAX_TARGETS = 64;        // targets of one image (BOP images have a few to ~20)
@@ -230,7 +215,7 @@ int upload(DevBuf& b, const void* src, size_t bytes, hipStream_t st)
 {
     int rc = b.reserve(std::max<size_t>(bytes, 1));
     if (rc) return rc;
-    if (bytes) RGBD_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
     return P2P_OK;
 }
 
@@ -258,8 +243,7 @@ int p2p_rgbd_create(p2p_ctx* ctx, p2p_rgbd** out)
 void p2p_rgbd_destroy(p2p_rgbd* h)
 {
     if (!h) return;
-    hipSetDevice(h->device);           // hipFree waits for the work that reads the buffers; the context itself may be gone already
-    h->release_all();
+    hipSetDevice(h->device);           // the buffers' hipFree waits for the work that reads them; the context itself may be gone already
     delete h;
 }
 
@@ -284,9 +268,9 @@ int p2p_rgbd_load(p2p_rgbd* h, const unsigned char* const* rgb, const void* cons
             return P2P_ERR_INVALID_ARG;
         }
     Ctx& X = *h->ctx;
-    RGBD_TRY(hipSetDevice(X.device));
+    HIP_TRY(hipSetDevice(X.device));
     hipStream_t st = X.stream;
-    RGBD_TRY(hipStreamSynchronize(st));           // queued work of the previous chunk may still read the buffers
+    HIP_TRY(hipStreamSynchronize(st));           // queued work of the previous chunk may still read the buffers
     const size_t HW = (size_t)height * width, esz = depth_dtype == P2P_DEPTH_U16 ? 2 : 4;
     int rc;
     h->n_images = 0;
@@ -298,30 +282,23 @@ int p2p_rgbd_load(p2p_rgbd* h, const unsigned char* const* rgb, const void* cons
     std::vector<float> sc(n_images);
     for (int i = 0; i < n_images; ++i) {
         sc[i] = (float)depth_scale[i];             // numpy: float32 array * Python float -> the float is taken as float32
-        RGBD_TRY(hipMemcpyAsync(h->raw.as<char>() + i * HW * esz, depth[i], HW * esz, hipMemcpyHostToDevice, st));
-        RGBD_TRY(hipMemcpyAsync(h->rgb.as<unsigned char>() + i * HW * 3, rgb[i], HW * 3, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->raw.as<char>() + i * HW * esz, depth[i], HW * esz, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->rgb.as<unsigned char>() + i * HW * 3, rgb[i], HW * 3, hipMemcpyHostToDevice, st));
     }
-    if (n_masks) RGBD_TRY(hipMemcpyAsync(h->det.p, masks, n_masks * HW, hipMemcpyHostToDevice, st));
+    if (n_masks) HIP_TRY(hipMemcpyAsync(h->det.p, masks, n_masks * HW, hipMemcpyHostToDevice, st));
     DevBuf dsc;
     if ((rc = dsc.reserve(sizeof(float) * n_images))) return rc;
-    hipError_t e = hipMemcpyAsync(dsc.p, sc.data(), sizeof(float) * n_images, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((HW + PREP_THREADS - 1) / PREP_THREADS), n_images);
-        if (depth_dtype == P2P_DEPTH_U16)
-            prepare_kernel<unsigned short><<<grid, PREP_THREADS, 0, st>>>(h->raw.as<unsigned short>(), h->rgb.as<unsigned char>(),
-                                                                        dsc.as<float>(), HW, h->dt.as<float>(), h->dv.as<unsigned char>(),
-                                                                        h->frame.as<float>());
-        else
-            prepare_kernel<float><<<grid, PREP_THREADS, 0, st>>>(h->raw.as<float>(), h->rgb.as<unsigned char>(), dsc.as<float>(), HW,
-                                                               h->dt.as<float>(), h->dv.as<unsigned char>(), h->frame.as<float>());
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    dsc.release();
-    if (e != hipSuccess) {
-        set_error("%s: %s", who, hipGetErrorString(e));
-        return P2P_ERR_HIP;
-    }
+    HIP_TRY(hipMemcpyAsync(dsc.p, sc.data(), sizeof(float) * n_images, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((HW + PREP_THREADS - 1) / PREP_THREADS), n_images);
+    if (depth_dtype == P2P_DEPTH_U16)
+        prepare_kernel<unsigned short><<<grid, PREP_THREADS, 0, st>>>(h->raw.as<unsigned short>(), h->rgb.as<unsigned char>(),
+                                                                    dsc.as<float>(), HW, h->dt.as<float>(), h->dv.as<unsigned char>(),
+                                                                    h->frame.as<float>());
+    else
+        prepare_kernel<float><<<grid, PREP_THREADS, 0, st>>>(h->raw.as<float>(), h->rgb.as<unsigned char>(), dsc.as<float>(), HW,
+                                                           h->dt.as<float>(), h->dv.as<unsigned char>(), h->frame.as<float>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
     h->n_images = n_images;
     h->H = height;
     h->W = width;
@@ -351,12 +328,12 @@ int p2p_rgbd_read(p2p_rgbd* h, int i, float* depth_t, unsigned char* depth_valid
         return P2P_ERR_INVALID_ARG;
     }
     Ctx& X = *h->ctx;
-    RGBD_TRY(hipSetDevice(X.device));
+    HIP_TRY(hipSetDevice(X.device));
     const size_t HW = (size_t)h->H * h->W;
-    if (depth_t) RGBD_TRY(hipMemcpyAsync(depth_t, h->dt.as<float>() + i * HW, HW * 4, hipMemcpyDeviceToHost, X.stream));
-    if (depth_valid) RGBD_TRY(hipMemcpyAsync(depth_valid, h->dv.as<unsigned char>() + i * HW, HW, hipMemcpyDeviceToHost, X.stream));
-    if (frame) RGBD_TRY(hipMemcpyAsync(frame, h->frame.as<float>() + i * HW * 3, HW * 12, hipMemcpyDeviceToHost, X.stream));
-    RGBD_TRY(hipStreamSynchronize(X.stream));
+    if (depth_t) HIP_TRY(hipMemcpyAsync(depth_t, h->dt.as<float>() + i * HW, HW * 4, hipMemcpyDeviceToHost, X.stream));
+    if (depth_valid) HIP_TRY(hipMemcpyAsync(depth_valid, h->dv.as<unsigned char>() + i * HW, HW, hipMemcpyDeviceToHost, X.stream));
+    if (frame) HIP_TRY(hipMemcpyAsync(frame, h->frame.as<float>() + i * HW * 3, HW * 12, hipMemcpyDeviceToHost, X.stream));
+    HIP_TRY(hipStreamSynchronize(X.stream));
     return P2P_OK;
 }
 
@@ -376,7 +353,7 @@ int p2p_rgbd_refine(p2p_rgbd* h, const p2p_mesh* const* meshes, int n_meshes, co
         }
     }
     Ctx& X = *h->ctx;
-    RGBD_TRY(hipSetDevice(X.device));
+    HIP_TRY(hipSetDevice(X.device));
     hipStream_t st = X.stream;
     const size_t HW = (size_t)h->H * h->W;
     h->n_rec = 0;
@@ -388,13 +365,13 @@ int p2p_rgbd_refine(p2p_rgbd* h, const p2p_mesh* const* meshes, int n_meshes, co
         if ((rc = h->umask.reserve(n_jobs * HW)) || (rc = h->ucount.reserve(8 * n_jobs)) ||
             (rc = upload(h->jmeta, meta.data(), sizeof(int) * 2 * n_jobs, st)))
             return rc;
-        RGBD_TRY(hipMemsetAsync(h->ucount.p, 0, 8 * n_jobs, st));
+        HIP_TRY(hipMemsetAsync(h->ucount.p, 0, 8 * n_jobs, st));
         const unsigned bx = (unsigned)std::min<size_t>(64, (HW + UNION_THREADS * 16 - 1) / (UNION_THREADS * 16));
         union_kernel<<<dim3(bx, n_jobs), UNION_THREADS, 0, st>>>(h->det.as<unsigned char>(), h->dv.as<unsigned char>(), h->jmeta.as<int>(),
                                                                  HW, h->umask.as<unsigned char>(), h->ucount.as<unsigned long long>());
-        RGBD_TRY(hipGetLastError());
-        RGBD_TRY(hipMemcpyAsync(cnt.data(), h->ucount.p, 8 * n_jobs, hipMemcpyDeviceToHost, st));
-        RGBD_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(cnt.data(), h->ucount.p, 8 * n_jobs, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     // the union gate (:457-459) before the ICP; the rest go through the chain of p2p_refine_depth_batch on device inputs
     std::vector<p2p_refine_job> sub;
@@ -436,11 +413,11 @@ int p2p_rgbd_refine(p2p_rgbd* h, const p2p_mesh* const* meshes, int n_meshes, co
         if (inlier_masks) {
             for (int j = 0; j < n_jobs; ++j) {
                 const int k = h->recmask_host[j];
-                if (k >= 0) RGBD_TRY(hipMemcpyAsync(inlier_masks + j * HW, h->inl.as<unsigned char>() + k * HW, HW, hipMemcpyDeviceToHost, st));
+                if (k >= 0) HIP_TRY(hipMemcpyAsync(inlier_masks + j * HW, h->inl.as<unsigned char>() + k * HW, HW, hipMemcpyDeviceToHost, st));
                 else std::memset(inlier_masks + j * HW, 0, HW);
             }
         }
-        RGBD_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     h->n_rec = n_jobs;
     return P2P_OK;
@@ -498,7 +475,7 @@ int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tgt_off, c
                 return P2P_ERR_INVALID_ARG;
             }
     Ctx& X = *h->ctx;
-    RGBD_TRY(hipSetDevice(X.device));
+    HIP_TRY(hipSetDevice(X.device));
     hipStream_t st = X.stream;
     const size_t HW = (size_t)h->H * h->W;
     int rc;
@@ -514,11 +491,11 @@ int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tgt_off, c
     if ((rc = h->rin.reserve(sbytes + sizeof(double) * std::max(nr, 1))) || (rc = h->rout.reserve(sizeof(double) * ROW * std::max(nr, 1))) ||
         (rc = h->err.reserve(sizeof(int))))
         return rc;
-    RGBD_TRY(hipMemcpyAsync(h->rin.p, pk.data(), sizeof(int) * nint, hipMemcpyHostToDevice, st));
-    if (nr) RGBD_TRY(hipMemcpyAsync(h->rin.as<char>() + sbytes, roi_score, sizeof(double) * nr, hipMemcpyHostToDevice, st));
-    RGBD_TRY(hipMemsetAsync(h->rout.p, 0, sizeof(double) * ROW * std::max(nr, 1), st));
-    RGBD_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
-    if (round == 0) RGBD_TRY(hipMemsetAsync(h->occ.p, 0, n_images * HW, st));
+    HIP_TRY(hipMemcpyAsync(h->rin.p, pk.data(), sizeof(int) * nint, hipMemcpyHostToDevice, st));
+    if (nr) HIP_TRY(hipMemcpyAsync(h->rin.as<char>() + sbytes, roi_score, sizeof(double) * nr, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->rout.p, 0, sizeof(double) * ROW * std::max(nr, 1), st));
+    HIP_TRY(hipMemsetAsync(h->err.p, 0, sizeof(int), st));
+    if (round == 0) HIP_TRY(hipMemsetAsync(h->occ.p, 0, n_images * HW, st));
     const p2p_refine_result* rec = h->rec.as<p2p_refine_result>();
     const int* recmask = h->recmask.as<int>();
     const unsigned char* inl = h->inl.as<unsigned char>();
@@ -529,7 +506,7 @@ int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tgt_off, c
             (rc = upload(h->hrecmask, rm.data(), sizeof(int) * n_records, st)) ||
             (host_masks && (rc = upload(h->hmask, host_masks, n_records * HW, st))))
             return rc;
-        RGBD_TRY(hipStreamSynchronize(st));       // rm is a local
+        HIP_TRY(hipStreamSynchronize(st));       // rm is a local
         rec = h->hrec.as<p2p_refine_result>();
         recmask = h->hrecmask.as<int>();
         inl = h->hmask.as<unsigned char>();
@@ -550,13 +527,13 @@ int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tgt_off, c
     a.rows = h->rout.as<double>();
     a.err = h->err.as<int>();
     resolve_kernel<<<n_images, RESOLVE_THREADS, 0, st>>>(a);
-    RGBD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int err = 0;
     std::vector<int> back(nint);
-    RGBD_TRY(hipMemcpyAsync(back.data(), h->rin.p, sizeof(int) * nint, hipMemcpyDeviceToHost, st));
-    if (nr) RGBD_TRY(hipMemcpyAsync(rows, h->rout.p, sizeof(double) * ROW * nr, hipMemcpyDeviceToHost, st));
-    RGBD_TRY(hipMemcpyAsync(&err, h->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    RGBD_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(back.data(), h->rin.p, sizeof(int) * nint, hipMemcpyDeviceToHost, st));
+    if (nr) HIP_TRY(hipMemcpyAsync(rows, h->rout.p, sizeof(double) * ROW * nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err, h->err.p, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (nr) std::memcpy(roi_used, back.data() + at[10], sizeof(int) * nr);
     if (nt) std::memcpy(inst_pred, back.data() + at[11], sizeof(int) * nt);
     if (err) {
