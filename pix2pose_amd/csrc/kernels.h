@@ -15,19 +15,29 @@ inline const char* dev_env(const char* name) { return getenv(name); }
 inline const char* dev_env(const char*) { return nullptr; }
 #endif
 
-// Measurement hook of the glue / PnP launches (p2p_profile_*, slots 12..19 of p2p_mi355.h): the entry points of the pipeline set it while
-// profiling is enabled on their context; a ProfScope around a launch then brackets it with HIP events on the stream it is launched on.
-struct ProfHook {
-    void* ctx;
-    void (*begin)(void* ctx, int slot, hipStream_t s);
-    void (*end)(void* ctx, hipStream_t s);
-};
-extern thread_local ProfHook g_prof_hook;
+// One measured launch (p2p_profile_*): while `ctx` is set, the launches enqueued on `s` during the scope's lifetime are bracketed by a pair
+// of HIP events, counted in `slot` with the given algorithmic work when the scope closes (model.hip: prof_harvest).  A pair that cannot be
+// created or recorded goes back to the context's pool and the scope measures nothing (ok() says so).
+struct Ctx;
+// The glue / PnP launches (slots 12..19 of p2p_mi355.h) take their context from the calling thread: the entry points of the pipeline set it
+// while profiling is enabled on their context (model.h: GlueProfGuard).
+extern thread_local Ctx* g_prof_ctx;
 struct ProfScope {
+    Ctx* ctx;              // null: not measuring
     hipStream_t s;
-    bool on;
-    ProfScope(int slot, hipStream_t st) : s(st), on(g_prof_hook.ctx != nullptr) { if (on) g_prof_hook.begin(g_prof_hook.ctx, slot, s); }
-    ~ProfScope() { if (on) g_prof_hook.end(g_prof_hook.ctx, s); }
+    int slot;
+    double flops, bytes;
+    hipEvent_t a = nullptr, b = nullptr;
+    bool failed = false;
+    ProfScope(Ctx* X, int slot_, hipStream_t st, double fl = 0.0, double by = 0.0) : ctx(X), s(st), slot(slot_), flops(fl), bytes(by) { if (ctx) open(); }
+    ProfScope(int slot_, hipStream_t st) : ProfScope(g_prof_ctx, slot_, st) {}
+    ~ProfScope() { if (ctx) (void)close(); }
+    ProfScope(const ProfScope&) = delete;
+    ProfScope& operator=(const ProfScope&) = delete;
+    bool ok() const { return !failed; }
+    void open();
+    // records the closing event and queues the pair (keep), or gives the pair back (a launch that failed); hipSuccess when not measuring
+    hipError_t close(bool keep = true);
 };
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_LEAKY = 2 };
@@ -206,7 +216,7 @@ bool wino_supported(int H, int W, int Cin0, int Cin1, int Cout);
 size_t wino_v_bytes(int N, int H, int W, int Cin);
 int wino_gemm_grid(const WinoParams& p);
 hipError_t launch_wino_input(const WinoParams& p, hipStream_t s);
-hipError_t launch_wino_gemm(const WinoParams& p, hipStream_t s);
+hipError_t launch_wino_gemm(const WinoParams& p, int n_cu, hipStream_t s);      // n_cu: compute units of the device (persistent grid)
 
 // Winograd F(4,3) along the row axis for Conv2DTranspose 5x5 stride 2 'SAME' (wino3.hip): the four sub-pixel phases as 3-tap correlations on
 // the input grid sharing ONE input transform -- 15 position-products per input pixel instead of 25.  Two launches like wino.hip: the input
@@ -231,7 +241,7 @@ struct Wino3Params {
 bool wino3_supported(int H, int W, int Cin, int Cout);
 size_t wino3_v_bytes(int N, int H, int W, int Cin);
 hipError_t launch_wino3_input(const Wino3Params& p, hipStream_t s);
-hipError_t launch_wino3_gemm(const Wino3Params& p, hipStream_t s);
+hipError_t launch_wino3_gemm(const Wino3Params& p, int n_cu, hipStream_t s);
 
 // The same F(4,3) form for the two stride-2 layers on an 8x8 grid (wino3o.hip): mode 0 = Conv2DTranspose 5x5 / 2 (up1: 8x8 -> 16x16, panel of
 // pack_wino3), mode 1 = Conv2D 5x5 / 2 'SAME' (conv4: 16x16 -> 8x8 through the four parity planes, panel of pack_wino3_s2:
@@ -259,7 +269,7 @@ bool wino3o_supported(int mode, int Cin, int Cout);
 size_t wino3o_v_bytes(int mode, int units, int Cin);
 int wino3o_units(const Wino3oParams& p);
 hipError_t launch_wino3o_input(const Wino3oParams& p, int mode, hipStream_t s);
-hipError_t launch_wino3o_gemm(const Wino3oParams& p, int mode, hipStream_t s);
+hipError_t launch_wino3o_gemm(const Wino3oParams& p, int mode, int n_cu, hipStream_t s);
 
 // Small-batch variant (igemm_stream.hip): one wave per 32x32 / 64x32 output tile, operands streamed global -> registers with a deep
 // software pipeline.  Bit-identical to the batched kernel that serves the layer: every output element is the same chain of MFMAs over

@@ -90,6 +90,7 @@ struct Ctx {
     float* prob_stage = nullptr;
     Pipeline* pipe = nullptr;
     int wino_mode = P2P_WINOGRAD_AUTO;    // p2p_ctx_set_winograd
+    int n_cu = 0;                         // compute units of the device (the persistent Winograd GEMM launches)
     int dev_part = 0;                     // timing builds only (P2P_TIMING_SWITCHES): run a part of the generator pass
     // operand-range guard (kernels.h): device words raised by the epilogues of split-f16 passes.  Word 0: direct forward calls
     // (p2p_predict / p2p_forward_async), words 1.. : one per est_pose batch slot.  range_cur = where the passes being enqueued report.
@@ -109,11 +110,11 @@ struct Ctx {
     ~Ctx();
 };
 
-// Sets the glue / PnP measurement hook (kernels.h: ProfHook) for the calling thread while the context is profiling.
-struct ProfHookGuard {
-    ProfHook prev;
-    explicit ProfHookGuard(Ctx& X);
-    ~ProfHookGuard();
+// Makes the context the one the glue / PnP launches of the calling thread are measured in (kernels.h: g_prof_ctx) while it is profiling.
+struct GlueProfGuard {
+    Ctx* prev;
+    explicit GlueProfGuard(Ctx& X);
+    ~GlueProfGuard();
 };
 
 int forward_chunk(Ctx& X, const Model& M, const float* x_dev, int n, float* xyzp_dev);

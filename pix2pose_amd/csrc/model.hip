@@ -11,7 +11,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <thread>
 
 namespace p2p {
@@ -844,6 +843,74 @@ struct PreparedConv {
     double flops = 0, bytes = 0;
 };
 
+// One launch of the generator on the lane's stream, measured in `slot` while the context is profiling: launch() returns the launcher's
+// hipError_t.  While profiling, a launch whose event pair cannot be created or recorded fails (P2P_ERR_HIP).
+template <class F> static int prof_launch(Ctx& X, int slot, double flops, double bytes, F&& launch)
+{
+    ProfScope ps(X.profiling ? &X : nullptr, slot, X.cur->stream, flops, bytes);
+    if (!ps.ok()) return P2P_ERR_HIP;
+    const hipError_t e = launch();
+    const hipError_t pe = ps.close(e == hipSuccess);
+    HIP_TRY(e);
+    HIP_TRY(pe);
+    return P2P_OK;
+}
+
+// The objects of the grouped pass being enqueued (X.grp, sorted by object) as seen by one launch: 0 for a single-object pass (the launch
+// takes its one object's panels from its own parameters), else their number -- P2P_ERR_CAPACITY beyond the IGEMM_MAX_GROUPS entries of a
+// launch's group table.
+static int pass_groups(const Ctx& X, const char* who)
+{
+    if (!X.grp || X.grp->models.size() <= 1) return 0;
+    const int ng = (int)X.grp->models.size();
+    if (ng > IGEMM_MAX_GROUPS) { set_error("%s: %d object groups exceed IGEMM_MAX_GROUPS", who, ng); return P2P_ERR_CAPACITY; }
+    return ng;
+}
+
+// Object g's copy of layer L, or null when it does not fit the launch chosen for L: another precision or (wino) no Winograd panel.
+static const ConvLayer* group_layer(const Ctx& X, int g, const ConvLayer& L, bool wino)
+{
+    const ConvLayer& Lg = X.grp->models[g]->L.at(L.name);
+    return Lg.prec != L.prec || (wino && !Lg.wino_u) ? nullptr : &Lg;
+}
+static int group_mismatch(const char* who) { set_error("%s: objects of one grouped pass must share a precision", who); return P2P_ERR_INVALID_ARG; }
+
+// Group table of a grouped Winograd launch: object g's samples start at its first unit of `per_unit` samples (a unit never straddles two
+// objects).  A single-object pass leaves n_groups at 0.
+static int wino_groups(const Ctx& X, const ConvLayer& L, int per_unit, const char* who, WinoGroup* grp, int& n_groups)
+{
+    const int ng = pass_groups(X, who);
+    if (ng <= 0) return ng;
+    const GroupCtx& G = *X.grp;
+    int unit0 = 0;
+    for (int g = 0; g < ng; ++g) {
+        const ConvLayer* Lg = group_layer(X, g, L, true);
+        if (!Lg) return group_mismatch(who);
+        grp[g] = {Lg->wino_u, Lg->wino_scale, Lg->shift, G.start[g], unit0};
+        unit0 += (G.start[g + 1] - G.start[g] + per_unit - 1) / per_unit;
+    }
+    grp[ng] = {nullptr, nullptr, nullptr, G.start[ng], unit0};
+    n_groups = ng;
+    return P2P_OK;
+}
+
+// Group table of a launch over all n samples of the pass (conv1.hip's first layer, the grouped split-K reduce): rows [start[g], start[g + 1])
+// take object g's copy of layer L -- its panel, scale (`wino`: the Winograd panel's) and shift.  A single-object pass is one group.
+static int conv1_groups(const Ctx& X, const ConvLayer& L, int n, int rows_per_sample, bool wino, Conv1Groups& G)
+{
+    const int ng = pass_groups(X, "forward");
+    if (ng < 0) return ng;
+    G.n_groups = ng ? ng : 1;
+    for (int g = 0; g < G.n_groups; ++g) {
+        const ConvLayer* Lg = ng ? group_layer(X, g, L, wino) : &L;
+        if (!Lg) return group_mismatch("forward");
+        G.start[g] = (ng ? X.grp->start[g] : 0) * rows_per_sample;
+        G.w[g] = Lg->w; G.scale[g] = wino ? Lg->wino_scale : Lg->scale; G.shift[g] = Lg->shift;
+    }
+    G.start[G.n_groups] = n * rows_per_sample;
+    return P2P_OK;
+}
+
 static int prepare_conv(Ctx& X, const ConvLayer& L, const ConvCall& c, PreparedConv& pc)
 {
     IgemmParams& p = pc.p;
@@ -889,15 +956,16 @@ static int prepare_conv(Ctx& X, const ConvLayer& L, const ConvCall& c, PreparedC
     p.prec = L.prec;
     p.range_acc = (L.prec == PREC_F16X3 && c.mode == EPI_NORMAL) ? X.range_cur : nullptr;      // the heads' outputs are bounded (tanh / sigmoid)
     const int cfg = L.Cout > 64 ? 0 : (L.Cout > 32 ? 1 : 2);      // 128x128 / 128x64 / 128x32 tiles
-    if (X.grp && X.grp->models.size() > 1) {
+    const int ng = pass_groups(X, "run_conv");
+    if (ng < 0) return ng;
+    if (ng) {
         const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size(), BM = igemm_tile_m(cfg), rows_per_sample = c.Hg * c.Wg;
-        if (ng > IGEMM_MAX_GROUPS) { set_error("run_conv: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
+        const int BM = igemm_tile_m(cfg), rows_per_sample = c.Hg * c.Wg;
         int tile0 = 0;
         for (int g = 0; g < ng; ++g) {
-            const ConvLayer& Lg = G.models[g]->L.at(L.name);
-            if (Lg.prec != L.prec) { set_error("run_conv: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Lg.w, Lg.scale, Lg.shift, G.start[g] * rows_per_sample, tile0};
+            const ConvLayer* Lg = group_layer(X, g, L, false);
+            if (!Lg) return group_mismatch("run_conv");
+            p.grp[g] = {Lg->w, Lg->scale, Lg->shift, G.start[g] * rows_per_sample, tile0};
             tile0 += ((G.start[g + 1] - G.start[g]) * rows_per_sample + BM - 1) / BM;
         }
         p.grp[ng] = {nullptr, nullptr, nullptr, G.start[ng] * rows_per_sample, tile0};
@@ -968,21 +1036,11 @@ static int launch_prepared(Ctx& X, const PreparedConv* pc, int n)
         for (int i = 0; i < n; ++i) stream_phase_of(pc[i].p, pc[i].so, &mp.ph[i]);
     } else if (n != 1) { set_error("launch_prepared: only streaming launches merge"); return P2P_ERR_INVALID_ARG; }
     const IgemmParams& p = c0.p;
-    auto launch = [&]() { return c0.stream ? launch_igemm_stream(p, mp, st) : c0.halo ? launch_heads_halo(p, st) : c0.halo_conv ? launch_igemm_halo(p, st) :
-                                 c0.halo8 ? launch_igemm_halo8(p, st) : c0.halo_s2 ? launch_igemm_halo_s2(p, st) : launch_igemm(p, c0.cfg, st); };
-    if (X.profiling) {
-        double fl = 0, by = 0;
-        for (int i = 0; i < n; ++i) { fl += pc[i].flops; by += pc[i].bytes; }
-        Ctx::ProfEvent ev{X.prof_get_event(), X.prof_get_event(), c0.prof_slot, fl, by};
-        if (!ev.a || !ev.b) return P2P_ERR_HIP;
-        HIP_TRY(hipEventRecord(ev.a, st));
-        HIP_TRY(launch());
-        HIP_TRY(hipEventRecord(ev.b, st));
-        X.prof_pending.push_back(ev);
-        return P2P_OK;
-    }
-    HIP_TRY(launch());
-    return P2P_OK;
+    double fl = 0, by = 0;
+    for (int i = 0; i < n; ++i) { fl += pc[i].flops; by += pc[i].bytes; }
+    return prof_launch(X, c0.prof_slot, fl, by, [&]() {
+        return c0.stream ? launch_igemm_stream(p, mp, st) : c0.halo ? launch_heads_halo(p, st) : c0.halo_conv ? launch_igemm_halo(p, st) :
+               c0.halo8 ? launch_igemm_halo8(p, st) : c0.halo_s2 ? launch_igemm_halo_s2(p, st) : launch_igemm(p, c0.cfg, st); });
 }
 
 static bool small_split_route() { static const bool on = dev_env("P2P_NO_SMALL_SPLIT") == nullptr; return on; }     // development builds: A/B against the single chain
@@ -1051,22 +1109,6 @@ static int conv_layer(Ctx& X, const ConvLayer& L, const float* in, int N, int H,
 // (p2p_ctx_set_winograd: off / auto / always), not a development switch.
 constexpr int WINO_MIN_INPUTS = 1;
 
-static int timed_launch(Ctx& X, int slot, double flops, double bytes, const std::function<hipError_t()>& launch)
-{
-    hipStream_t st = X.cur->stream;
-    if (X.profiling) {
-        Ctx::ProfEvent ev{X.prof_get_event(), X.prof_get_event(), slot, flops, bytes};
-        if (!ev.a || !ev.b) return P2P_ERR_HIP;
-        HIP_TRY(hipEventRecord(ev.a, st));
-        HIP_TRY(launch());
-        HIP_TRY(hipEventRecord(ev.b, st));
-        X.prof_pending.push_back(ev);
-        return P2P_OK;
-    }
-    HIP_TRY(launch());
-    return P2P_OK;
-}
-
 static bool wino_split_route() { static const bool on = dev_env("P2P_NO_WINO_SPLIT") == nullptr; return on; }     // development builds: A/B against the single chain
 
 // 0 = not for this route (the caller falls through to the direct kernels), 1 = done, < 0 = error
@@ -1088,20 +1130,8 @@ static int try_wino(Ctx& X, const ConvLayer& L, const float* a, int Ca, const fl
     p.act = ACT_LEAKY; p.alpha = LEAKY;
     p.out = out; p.out_cstride = L.Cout; p.out_coff = 0;
     p.range_acc = X.range_cur;
-    if (X.grp && X.grp->models.size() > 1) {
-        const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size();
-        if (ng > IGEMM_MAX_GROUPS) { set_error("run_conv: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
-        int unit0 = 0;                  // 16x16 grids: two samples per workgroup, every object paired up on its own
-        for (int g = 0; g < ng; ++g) {
-            const ConvLayer& Lg = G.models[g]->L.at(L.name);
-            if (!Lg.wino_u || Lg.prec != PREC_F16X3) { set_error("run_conv: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Lg.wino_u, Lg.wino_scale, Lg.shift, G.start[g], unit0};
-            unit0 += (G.start[g + 1] - G.start[g] + 1) / 2;
-        }
-        p.grp[ng] = {nullptr, nullptr, nullptr, G.start[ng], unit0};
-        p.n_groups = ng;
-    }
+    int rc = wino_groups(X, L, 2, "try_wino", p.grp, p.n_groups);      // 16x16 grids: two samples per workgroup, every object paired up on its own
+    if (rc) return rc;
     static const int wino_min = dev_env("P2P_WINO_MIN") ? atoi(dev_env("P2P_WINO_MIN")) : WINO_MIN_INPUTS;
     if (X.wino_mode != P2P_WINOGRAD_ALWAYS && N < wino_min) return 0;
     // Launches under half a workgroup per CU (a pass over a few inputs; deconv1 up to 64): under "auto" the channel slices are cut into ranges,
@@ -1114,11 +1144,10 @@ static int try_wino(Ctx& X, const ConvLayer& L, const float* a, int Ca, const fl
     }
     hipStream_t st = X.cur->stream;
     const double in_el = (double)px * p.Cin, out_el = (double)px * L.Cout;
-    int rc = timed_launch(X, 11, 0.0, 4.0 * in_el + 8.0 * in_el, [&]() { return launch_wino_input(p, st); });
-    if (rc) return rc;
+    if ((rc = prof_launch(X, 11, 0.0, 4.0 * in_el + 8.0 * in_el, [&]() { return launch_wino_input(p, st); }))) return rc;
     // algorithmic work of the LAYER (the direct form's MACs, like every other slot); compulsory bytes: V once, the panel once, the output
-    rc = timed_launch(X, 10, 2.0 * out_el * 25.0 * p.Cin, 8.0 * in_el + (double)L.wino_bytes + 4.0 * out_el, [&]() { return launch_wino_gemm(p, st); });
-    if (rc) return rc;
+    if ((rc = prof_launch(X, 10, 2.0 * out_el * 25.0 * p.Cin, 8.0 * in_el + (double)L.wino_bytes + 4.0 * out_el,
+                          [&]() { return launch_wino_gemm(p, X.n_cu, st); }))) return rc;
     if (p.ksplit > 1) HIP_TRY(launch_splitk_reduce(p.partial, p.ksplit, (int)px, L.Cout, L.wino_scale, L.shift, ACT_LEAKY, LEAKY, out, X.range_cur, st));
     return 1;
 }
@@ -1169,20 +1198,8 @@ static int try_wino3o(Ctx& X, const ConvLayer& L, int mode, const float* in, int
     p.out = out; p.out_cstride = L.Cout; p.out_coff = 0;
     p.ksplit = 1;
     p.range_acc = X.range_cur;
-    if (X.grp && X.grp->models.size() > 1) {
-        const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size();
-        if (ng > IGEMM_MAX_GROUPS) { set_error("wino3o: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
-        int unit0 = 0;                  // eight samples per workgroup, every object grouped on its own
-        for (int g = 0; g < ng; ++g) {
-            const ConvLayer& Lg = G.models[g]->L.at(L.name);
-            if (!Lg.wino_u || Lg.prec != PREC_F16X3) { set_error("wino3o: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Lg.wino_u, Lg.wino_scale, Lg.shift, G.start[g], unit0};
-            unit0 += (G.start[g + 1] - G.start[g] + 7) / 8;
-        }
-        p.grp[ng] = {nullptr, nullptr, nullptr, G.start[ng], unit0};
-        p.n_groups = ng;
-    }
+    int rc = wino_groups(X, L, 8, "try_wino3o", p.grp, p.n_groups);      // eight samples per workgroup, every object grouped on its own
+    if (rc) return rc;
     const int units = wino3o_units(p);
     if (wino3o_v_bytes(mode, units, C) > (size_t)X.max_batch * 64 * 64 * 128 * 2 * sizeof(float)) return 0;      // (many objects of a few detections each: the padded units outgrow the V workspace)
     // conv4 on less than one workgroup per CU: K split over the four parity planes, the four partial sums added after the inverse transform.
@@ -1190,16 +1207,13 @@ static int try_wino3o(Ctx& X, const ConvLayer& L, int mode, const float* in, int
     if (mode == 1 && (X.wino_mode == P2P_WINOGRAD_ALWAYS || units * (L.Cout / 64) < 256)) { p.ksplit = 4; p.partial = X.cur->act["c3"]; }
     hipStream_t st = X.cur->stream;
     const double in_el = (double)N * (mode ? 256 : 64) * C, out_el = (double)N * (mode ? 64 : 256) * L.Cout;
-    int rc = timed_launch(X, 21, 0.0, 4.0 * in_el + 6.0 * in_el, [&]() { return launch_wino3o_input(p, mode, st); });
-    if (rc) return rc;
+    if ((rc = prof_launch(X, 21, 0.0, 4.0 * in_el + 6.0 * in_el, [&]() { return launch_wino3o_input(p, mode, st); }))) return rc;
     // algorithmic work of the LAYER: conv4 25 MACs per output element and input channel; up1 25 taps over its four phases = 6.25
-    rc = timed_launch(X, 20, 2.0 * out_el * (mode ? 25.0 : 6.25) * C, 6.0 * in_el + (double)L.wino_bytes + 4.0 * out_el, [&]() { return launch_wino3o_gemm(p, mode, st); });
-    if (rc) return rc;
+    if ((rc = prof_launch(X, 20, 2.0 * out_el * (mode ? 25.0 : 6.25) * C, 6.0 * in_el + (double)L.wino_bytes + 4.0 * out_el,
+                          [&]() { return launch_wino3o_gemm(p, mode, X.n_cu, st); }))) return rc;
     if (p.ksplit > 1 && p.n_groups > 1) {
         Conv1Groups G;
-        G.n_groups = p.n_groups;
-        for (int g = 0; g < p.n_groups; ++g) { G.start[g] = p.grp[g].sample0 * 64; G.w[g] = nullptr; G.scale[g] = p.grp[g].scale; G.shift[g] = p.grp[g].shift; }
-        G.start[p.n_groups] = N * 64;
+        if ((rc = conv1_groups(X, L, N, 64, true, G))) return rc;
         HIP_TRY(launch_splitk_reduce_groups(p.partial, p.ksplit, N * 64, L.Cout, G, ACT_LEAKY, LEAKY, out, X.range_cur, st));
     } else if (p.ksplit > 1)
         HIP_TRY(launch_splitk_reduce(p.partial, p.ksplit, N * 64, L.Cout, L.wino_scale, L.shift, ACT_LEAKY, LEAKY, out, X.range_cur, st));
@@ -1224,26 +1238,13 @@ static int try_wino3(Ctx& X, const ConvLayer& L, const float* in, int N, int H, 
     p.act = ACT_LEAKY; p.alpha = LEAKY;
     p.out = out; p.out_cstride = L.Cout; p.out_coff = 0;
     p.range_acc = X.range_cur;
-    if (X.grp && X.grp->models.size() > 1) {
-        const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size();
-        if (ng > IGEMM_MAX_GROUPS) { set_error("deconv_layer: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
-        int unit0 = 0;                  // 16x16 grids: two samples per workgroup, every object paired up on its own
-        for (int g = 0; g < ng; ++g) {
-            const ConvLayer& Lg = G.models[g]->L.at(L.name);
-            if (!Lg.wino_u || Lg.prec != PREC_F16X3) { set_error("deconv_layer: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Lg.wino_u, Lg.wino_scale, Lg.shift, G.start[g], unit0};
-            unit0 += (G.start[g + 1] - G.start[g] + 1) / 2;
-        }
-        p.grp[ng] = {nullptr, nullptr, nullptr, G.start[ng], unit0};
-        p.n_groups = ng;
-    }
+    int rc = wino_groups(X, L, 2, "try_wino3", p.grp, p.n_groups);      // 16x16 grids: two samples per workgroup, every object paired up on its own
+    if (rc) return rc;
     hipStream_t st = X.cur->stream;
     const double in_el = (double)px * C, out_el = 4.0 * (double)px * L.Cout;
-    int rc = timed_launch(X, 21, 0.0, 4.0 * in_el + 6.0 * in_el, [&]() { return launch_wino3_input(p, st); });
-    if (rc) return rc;
+    if ((rc = prof_launch(X, 21, 0.0, 4.0 * in_el + 6.0 * in_el, [&]() { return launch_wino3_input(p, st); }))) return rc;
     // algorithmic work of the LAYER: 25 taps over the four phases = 6.25 MACs per output element and input channel
-    rc = timed_launch(X, 20, 2.0 * out_el * 6.25 * C, 6.0 * in_el + (double)L.wino_bytes + 4.0 * out_el, [&]() { return launch_wino3_gemm(p, st); });
+    rc = prof_launch(X, 20, 2.0 * out_el * 6.25 * C, 6.0 * in_el + (double)L.wino_bytes + 4.0 * out_el, [&]() { return launch_wino3_gemm(p, X.n_cu, st); });
     return rc ? rc : 1;
 }
 
@@ -1284,75 +1285,31 @@ static bool fused_blocks() { static const bool on = dev_env("P2P_NO_FUSED_BLOCK"
 // smallest fused launch (workgroups): below it the three streaming launches run (development builds: P2P_FUSED_MIN_WGS)
 static int fused_min_wgs() { static const int v = dev_env("P2P_FUSED_MIN_WGS") ? atoi(dev_env("P2P_FUSED_MIN_WGS")) : -1; return v >= 0 ? v : stream_max_wgs() + 1; }
 
-static int run_resblock(const Model& M, Ctx& X, const std::string& n, const float* in, int N, int H, int f1, float* out)
+// One fused bottleneck block (resblock.hip): an identity block (stride 1, Cin = 4 f1, third layer _2c) or a projection block res2a / res3a
+// (proj: the shortcut folded into the third layer _2c1; H = input grid, Ho = H / stride the output grid).
+static int run_fused_block(const Model& M, Ctx& X, const std::string& n, const float* in, int N, int H, int Cin, int f1, int stride, bool proj, float* out)
 {
-    const ConvLayer &a = M.L.at(n + "_2a"), &b = M.L.at(n + "_2b"), &c = M.L.at(n + "_2c");
-    const int C = 4 * f1;
-    ResBlockParams p;
-    memset(&p, 0, sizeof(p));
-    p.x = in; p.out = out; p.N = N; p.H = H; p.W = H;
-    const size_t xb = (size_t)N * H * H * C * sizeof(float);
-    if (xb >= 0xFFFFFFF0ull) { set_error("run_resblock: tensor exceeds the 4 GB buffer-descriptor range (lower max_batch)"); return P2P_ERR_CAPACITY; }
-    p.x_bytes = (unsigned)xb;
-    p.wa_bytes = (unsigned)((size_t)round_up(a.Cout, 128) * a.K * sizeof(float));
-    p.wb_bytes = (unsigned)((size_t)round_up(b.Cout, 128) * b.K * sizeof(float));
-    p.wc_bytes = (unsigned)((size_t)round_up(c.Cout, 128) * c.K * sizeof(float));
-    p.range_acc = X.range_cur;
-    if (X.grp && X.grp->models.size() > 1) {
-        const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size();
-        if (ng > IGEMM_MAX_GROUPS) { set_error("run_resblock: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
-        for (int g = 0; g < ng; ++g) {
-            const Model& Mg = *G.models[g];
-            if (Mg.prec != PREC_F16X3 || !Mg.block_ss.count(n)) { set_error("run_resblock: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Mg.L.at(n + "_2a").w, Mg.L.at(n + "_2b").w, Mg.L.at(n + "_2c").w, Mg.block_ss.at(n), G.start[g], 0, Mg.L.at(n + "_2b").w_frag};
-        }
-        p.grp[ng] = {nullptr, nullptr, nullptr, nullptr, G.start[ng], 0, nullptr};
-        p.n_groups = ng;
-    } else {
-        p.grp[0] = {a.w, b.w, c.w, M.block_ss.at(n), 0, 0, b.w_frag};
-        p.grp[1] = {nullptr, nullptr, nullptr, nullptr, N, 0, nullptr};
-        p.n_groups = 1;
-    }
-    hipStream_t st = X.cur->stream;
-    if (X.profiling) {
-        const double px = (double)N * H * H;
-        Ctx::ProfEvent ev{X.prof_get_event(), X.prof_get_event(), 9, 2.0 * px * ((double)C * f1 + 9.0 * f1 * f1 + (double)f1 * C),
-                          4.0 * (2.0 * px * C + (double)C * f1 * 2 + 9.0 * f1 * f1)};      // input once (it is also the residual), output once, the three panels
-        if (!ev.a || !ev.b) return P2P_ERR_HIP;
-        HIP_TRY(hipEventRecord(ev.a, st));
-        HIP_TRY(launch_resblock(p, f1, st));
-        HIP_TRY(hipEventRecord(ev.b, st));
-        X.prof_pending.push_back(ev);
-        return P2P_OK;
-    }
-    HIP_TRY(launch_resblock(p, f1, st));
-    return P2P_OK;
-}
-
-// The projection blocks res2a / res3a in the same kernel (resblock.hip, PROJ): H = input grid, Ho = H / stride the output grid.
-static int run_resproj(const Model& M, Ctx& X, const std::string& n, const float* in, int N, int H, int Cin, int f1, int stride, float* out)
-{
-    const ConvLayer &a = M.L.at(n + "_2a"), &b = M.L.at(n + "_2b"), &c = M.L.at(n + "_2c1");
+    const ConvLayer &a = M.L.at(n + "_2a"), &b = M.L.at(n + "_2b"), &c = M.L.at(n + (proj ? "_2c1" : "_2c"));
     const int C = 4 * f1, Ho = H / stride;
     ResBlockParams p;
     memset(&p, 0, sizeof(p));
     p.x = in; p.out = out; p.N = N; p.H = Ho; p.W = Ho;
     const size_t xb = (size_t)N * H * H * Cin * sizeof(float), ob = (size_t)N * Ho * Ho * C * sizeof(float);
-    if (xb >= 0xFFFFFFF0ull || ob >= 0xFFFFFFF0ull) { set_error("run_resproj: tensor exceeds the 4 GB buffer-descriptor range (lower max_batch)"); return P2P_ERR_CAPACITY; }
+    if (xb >= 0xFFFFFFF0ull || ob >= 0xFFFFFFF0ull) { set_error("run_fused_block: tensor exceeds the 4 GB buffer-descriptor range (lower max_batch)"); return P2P_ERR_CAPACITY; }
     p.x_bytes = (unsigned)xb;
     p.wa_bytes = (unsigned)((size_t)round_up(a.Cout, 128) * a.K * sizeof(float));
     p.wb_bytes = (unsigned)((size_t)round_up(b.Cout, 128) * b.K * sizeof(float));
     p.wc_bytes = (unsigned)((size_t)round_up(c.Cout, 128) * c.K * sizeof(float));
     p.range_acc = X.range_cur;
-    if (X.grp && X.grp->models.size() > 1) {
+    const int ng = pass_groups(X, "run_fused_block");
+    if (ng < 0) return ng;
+    if (ng) {
         const GroupCtx& G = *X.grp;
-        const int ng = (int)G.models.size();
-        if (ng > IGEMM_MAX_GROUPS) { set_error("run_resproj: %d object groups exceed IGEMM_MAX_GROUPS", ng); return P2P_ERR_CAPACITY; }
         for (int g = 0; g < ng; ++g) {
             const Model& Mg = *G.models[g];
-            if (Mg.prec != PREC_F16X3 || !Mg.block_ss.count(n)) { set_error("run_resproj: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-            p.grp[g] = {Mg.L.at(n + "_2a").w, Mg.L.at(n + "_2b").w, Mg.L.at(n + "_2c1").w, Mg.block_ss.at(n), G.start[g], 0, Mg.L.at(n + "_2b").w_frag};
+            const ConvLayer* bg = group_layer(X, g, b, false);
+            if (!bg || !Mg.block_ss.count(n)) return group_mismatch("run_fused_block");
+            p.grp[g] = {Mg.L.at(a.name).w, bg->w, Mg.L.at(c.name).w, Mg.block_ss.at(n), G.start[g], 0, bg->w_frag};
         }
         p.grp[ng] = {nullptr, nullptr, nullptr, nullptr, G.start[ng], 0, nullptr};
         p.n_groups = ng;
@@ -1361,20 +1318,12 @@ static int run_resproj(const Model& M, Ctx& X, const std::string& n, const float
         p.grp[1] = {nullptr, nullptr, nullptr, nullptr, N, 0, nullptr};
         p.n_groups = 1;
     }
-    hipStream_t st = X.cur->stream;
-    if (X.profiling) {
-        const double px = (double)N * Ho * Ho;
-        Ctx::ProfEvent ev{X.prof_get_event(), X.prof_get_event(), 9, 2.0 * px * ((double)Cin * f1 + 9.0 * f1 * f1 + (double)(f1 + Cin) * C),
-                          4.0 * (px * Cin + px * C + (double)Cin * f1 + 9.0 * f1 * f1 + (double)(f1 + Cin) * C)};      // the sampled input pixels once, the output once, the panels
-        if (!ev.a || !ev.b) return P2P_ERR_HIP;
-        HIP_TRY(hipEventRecord(ev.a, st));
-        HIP_TRY(launch_resproj(p, f1, st));
-        HIP_TRY(hipEventRecord(ev.b, st));
-        X.prof_pending.push_back(ev);
-        return P2P_OK;
-    }
-    HIP_TRY(launch_resproj(p, f1, st));
-    return P2P_OK;
+    // third layer: K = f1, + Cin with the folded shortcut.  Compulsory bytes: the (sampled) input pixels once -- an identity block's input
+    // is also its residual --, the output once, the three panels
+    const double px = (double)N * Ho * Ho;
+    return prof_launch(X, 9, 2.0 * px * ((double)Cin * f1 + 9.0 * f1 * f1 + (double)c.K * C),
+                       4.0 * (px * Cin + px * C + (double)Cin * f1 + 9.0 * f1 * f1 + (double)c.K * C),
+                       [&]() { return proj ? launch_resproj(p, f1, X.cur->stream) : launch_resblock(p, f1, X.cur->stream); });
 }
 
 static bool fused_proj_blocks() { static const bool on = dev_env("P2P_NO_FUSED_PROJ") == nullptr; return on; }      // development builds: res2a / res3a on three launches
@@ -1387,10 +1336,10 @@ static int res_block(const Model& M, Ctx& X, const std::string& n, const float* 
     if (shortcut && M.prec == PREC_F16X3 && M.L.count(n + "_2c1") && fused_blocks() && fused_proj_blocks() && M.block_ss.count(n) &&
         ((f1 == 64 && Cin == 64 && stride == 1) || (f1 == 128 && Cin == 256 && stride == 2)) && resblock_supported(f1, Ho, Ho) &&
         resblock_grid(f1, N, Ho, Ho) >= fused_min_wgs())
-        return run_resproj(M, X, n, in, N, H, Cin, f1, stride, out);
+        return run_fused_block(M, X, n, in, N, H, Cin, f1, stride, true, out);
     if (!shortcut && stride == 1 && M.prec == PREC_F16X3 && Cin == 4 * f1 && fused_blocks() && M.block_ss.count(n) && resblock_supported(f1, H, H) &&
         resblock_grid(f1, N, H, H) >= fused_min_wgs())
-        return run_resblock(M, X, n, in, N, H, f1, out);
+        return run_fused_block(M, X, n, in, N, H, Cin, f1, 1, false, out);
     float* ta = X.cur->act["t_a"];
     float* tb = X.cur->act["t_b"];
     if ((rc = conv_layer(X, M.L.at(n + "_2a"), in, N, H, H, Cin, stride, ta, ACT_RELU))) return rc;
@@ -1416,6 +1365,33 @@ static int res_block(const Model& M, Ctx& X, const std::string& n, const float* 
     return conv_layer(X, M.L.at(n + "_2c"), tb, N, Ho, Ho, f1, 1, out, ACT_RELU, res);
 }
 
+// The first layer (Cin = 3, 128x128 -> 64x64 at stride 2) of the n inputs into f1, then the optional 3x3/2 max-pool into `pool`: split-f16
+// models on the matrix cores (conv1.hip: one launch for every object, per-sample panel lookup, the max-pool fused), fp32 ones on the VALU
+// kernel (one launch per object, tiny).
+static int first_layer(Ctx& X, const Model& M, const float* x, int n, int KH, int Cout, int act, float* pool)
+{
+    hipStream_t st = X.cur->stream;
+    float* f1 = X.cur->act["f1"];
+    const ConvLayer& L = M.L.at("conv1");
+    if (L.prec == PREC_F16X3) {
+        Conv1Groups G;
+        const int rc = conv1_groups(X, L, n, 1, false, G);
+        if (rc) return rc;
+        HIP_TRY(launch_conv1_f16x3(x, n, KH, Cout, G, act, LEAKY, f1, pool, X.range_cur, st));
+        return P2P_OK;
+    }
+    const int ng = X.grp ? (int)X.grp->models.size() : 1;
+    for (int g = 0; g < ng; ++g) {
+        const ConvLayer& Lg = X.grp ? X.grp->models[g]->L.at("conv1") : L;
+        const int s0 = X.grp ? X.grp->start[g] : 0, s1 = X.grp ? X.grp->start[g + 1] : n;
+        // (7x7: the ResNet front's ZeroPadding2D(3); 5x5: TF 'SAME')
+        HIP_TRY(launch_conv_first(x + (size_t)s0 * 49152, s1 - s0, 128, 128, Lg.w, KH, 2, KH == 7 ? 3 : 1, Cout, Lg.scale, Lg.shift, act, LEAKY,
+                                  f1 + (size_t)s0 * 64 * 64 * Cout, 64, 64, st));
+    }
+    if (pool) HIP_TRY(launch_maxpool3s2(f1, n, 64, 64, Cout, pool, st));
+    return P2P_OK;
+}
+
 #ifdef P2P_TIMING_SWITCHES      // A/B builds only (tools/ab_build.sh model.hip -DP2P_TIMING_SWITCHES): timing experiments, results are garbage
 #define dev_part() (X.dev_part)      // per context, from P2P_DEV_PART at p2p_ctx_create: 1 = ResNet front only, 2 = everything after it only
 #endif
@@ -1427,33 +1403,13 @@ int forward_chunk(Ctx& X, const Model& M, const float* x, int n, float* xyzp)
     hipStream_t st = X.cur->stream;
     auto& A = X.cur->act;
     const int n_grp = X.grp ? (int)X.grp->models.size() : 1;
-    auto grp_model = [&](int g) -> const Model& { return X.grp ? *X.grp->models[g] : M; };
-    auto g0 = [&](int g) -> int { return X.grp ? X.grp->start[g] : (g == 0 ? 0 : n); };
     const float *s1, *s2, *s3;      // skip tensors and their pixel strides / channel offsets
     int s1_stride, s1_off, s1_C, s2_stride, s2_off, s3_stride, s3_off;
     if (M.backbone == P2P_BACKBONE_RESNET50) {
 #ifdef P2P_TIMING_SWITCHES
         if (dev_part() == 2) goto after_front;
 #endif
-        if (M.L.at("conv1").prec == PREC_F16X3) {       // matrix-core first layer: one launch, per-sample panel lookup
-            if (n_grp > IGEMM_MAX_GROUPS) { set_error("forward: %d object groups exceed IGEMM_MAX_GROUPS", n_grp); return P2P_ERR_CAPACITY; }
-            Conv1Groups G;
-            G.n_groups = n_grp;
-            for (int g = 0; g < n_grp; ++g) {
-                const ConvLayer& c1 = grp_model(g).L.at("conv1");
-                if (c1.prec != PREC_F16X3) { set_error("forward: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-                G.start[g] = g0(g); G.w[g] = c1.w; G.scale[g] = c1.scale; G.shift[g] = c1.shift;
-            }
-            G.start[n_grp] = n;
-            HIP_TRY(launch_conv1_f16x3(x, n, 7, 64, G, ACT_RELU, LEAKY, A["f1"], A["p1"], X.range_cur, st));      // + the max-pool (f1: skip channels)
-        } else {
-        for (int g = 0; g < n_grp; ++g) {      // VALU first layer: one launch per object (tiny)
-            const ConvLayer& c1 = grp_model(g).L.at("conv1");
-            HIP_TRY(launch_conv_first(x + (size_t)g0(g) * 49152, g0(g + 1) - g0(g), 128, 128, c1.w, 7, 2, 3, 64, c1.scale, c1.shift,
-                                      ACT_RELU, LEAKY, A["f1"] + (size_t)g0(g) * 64 * 64 * 64, 64, 64, st));
-        }
-        HIP_TRY(launch_maxpool3s2(A["f1"], n, 64, 64, 64, A["p1"], st));
-        }
+        if ((rc = first_layer(X, M, x, n, 7, 64, ACT_RELU, A["p1"]))) return rc;      // + the max-pool (f1: skip channels)
         if ((rc = res_block(M, X, "res2a", A["p1"], n, 32, 64, 64, 1, true, A["o_a"]))) return rc;
         if ((rc = res_block(M, X, "res2b", A["o_a"], n, 32, 256, 64, 1, false, A["o_b"]))) return rc;
         if ((rc = res_block(M, X, "res2c", A["o_b"], n, 32, 256, 64, 1, false, A["f2"]))) return rc;
@@ -1474,23 +1430,7 @@ int forward_chunk(Ctx& X, const Model& M, const float* x, int n, float* xyzp)
     } else {
         // ae_model.py:74-106: each level = two parallel 5x5/2 convs concatenated [_1 || _2];
         // the skip is the _2 half, i.e. the upper channels of the merged output.
-        if (M.L.at("conv1").prec == PREC_F16X3) {       // matrix-core first layer (conv1.hip): one launch, per-sample panel lookup
-            if (n_grp > IGEMM_MAX_GROUPS) { set_error("forward: %d object groups exceed IGEMM_MAX_GROUPS", n_grp); return P2P_ERR_CAPACITY; }
-            Conv1Groups G;
-            G.n_groups = n_grp;
-            for (int g = 0; g < n_grp; ++g) {
-                const ConvLayer& c1 = grp_model(g).L.at("conv1");
-                if (c1.prec != PREC_F16X3) { set_error("forward: objects of one grouped pass must share a precision"); return P2P_ERR_INVALID_ARG; }
-                G.start[g] = g0(g); G.w[g] = c1.w; G.scale[g] = c1.scale; G.shift[g] = c1.shift;
-            }
-            G.start[n_grp] = n;
-            HIP_TRY(launch_conv1_f16x3(x, n, 5, 128, G, ACT_LEAKY, LEAKY, A["f1"], nullptr, X.range_cur, st));
-        } else
-        for (int g = 0; g < n_grp; ++g) {
-            const ConvLayer& c1 = grp_model(g).L.at("conv1");
-            HIP_TRY(launch_conv_first(x + (size_t)g0(g) * 49152, g0(g + 1) - g0(g), 128, 128, c1.w, 5, 2, 1, 128, c1.scale, c1.shift,
-                                      ACT_LEAKY, LEAKY, A["f1"] + (size_t)g0(g) * 64 * 64 * 128, 64, 64, st));
-        }
+        if ((rc = first_layer(X, M, x, n, 5, 128, ACT_LEAKY, nullptr))) return rc;
         if ((rc = conv_layer(X, M.L.at("conv2"), A["f1"], n, 64, 64, 128, 2, A["f2"], ACT_LEAKY))) return rc;
         if ((rc = conv_layer(X, M.L.at("conv3"), A["f2"], n, 32, 32, 256, 2, A["f3"], ACT_LEAKY))) return rc;
         if ((rc = try_wino3o(X, M.L.at("conv4"), 1, A["f3"], n, 256, A["f4"])) < 0) return rc;
@@ -1512,14 +1452,8 @@ int forward_chunk(Ctx& X, const Model& M, const float* x, int n, float* xyzp)
             HIP_TRY(launch_splitk_reduce(A["part"], 32, n, 256, L.scale, L.shift, ACT_NONE, LEAKY, A["enc"], M.prec == PREC_F16X3 ? X.range_cur : nullptr, st));
         } else {
             // per-object bias: every row is reduced with its own object's shift, one launch for the batch
-            if (n_grp > IGEMM_MAX_GROUPS) { set_error("forward: %d object groups exceed IGEMM_MAX_GROUPS", n_grp); return P2P_ERR_CAPACITY; }
             Conv1Groups G;
-            G.n_groups = n_grp;
-            for (int g = 0; g < n_grp; ++g) {
-                const ConvLayer& Lg = grp_model(g).L.at("dense_enc");
-                G.start[g] = g0(g); G.w[g] = nullptr; G.scale[g] = Lg.scale; G.shift[g] = Lg.shift;
-            }
-            G.start[n_grp] = n;
+            if ((rc = conv1_groups(X, L, n, 1, false, G))) return rc;
             HIP_TRY(launch_splitk_reduce_groups(A["part"], 32, n, 256, G, ACT_NONE, LEAKY, A["enc"], M.prec == PREC_F16X3 ? X.range_cur : nullptr, st));
         }
     }
@@ -1561,26 +1495,41 @@ int forward_async(Ctx& X, const Model& M, const float* x_dev, int n, float* xyzp
     return P2P_OK;
 }
 
-thread_local ProfHook g_prof_hook = {nullptr, nullptr, nullptr};
-static thread_local Ctx::ProfEvent g_open_ev;
-static void prof_hook_begin(void* c, int slot, hipStream_t s)
+thread_local Ctx* g_prof_ctx = nullptr;
+
+void ProfScope::open()
 {
-    Ctx& X = *static_cast<Ctx*>(c);
-    g_open_ev = Ctx::ProfEvent{X.prof_get_event(), X.prof_get_event(), slot, 0.0, 0.0};
-    if (g_open_ev.a) (void)hipEventRecord(g_open_ev.a, s);
+    a = ctx->prof_get_event();
+    b = a ? ctx->prof_get_event() : nullptr;
+    hipError_t e = hipSuccess;
+    if (a && b && (e = hipEventRecord(a, s)) == hipSuccess) return;
+    if (e != hipSuccess) set_error("hipEventRecord failed: %s", hipGetErrorString(e));
+    if (a) ctx->prof_pool.push_back(a);
+    if (b) ctx->prof_pool.push_back(b);
+    ctx = nullptr;
+    failed = true;
 }
-static void prof_hook_end(void* c, hipStream_t s)
+
+hipError_t ProfScope::close(bool keep)
 {
-    Ctx& X = *static_cast<Ctx*>(c);
-    if (!g_open_ev.a || !g_open_ev.b) return;
-    (void)hipEventRecord(g_open_ev.b, s);
-    X.prof_pending.push_back(g_open_ev);
+    Ctx* X = ctx;
+    ctx = nullptr;
+    if (!X) return hipSuccess;
+    const hipError_t e = keep ? hipEventRecord(b, s) : hipSuccess;
+    if (keep && e == hipSuccess) {
+        X->prof_pending.push_back(Ctx::ProfEvent{a, b, slot, flops, bytes});
+        return hipSuccess;
+    }
+    X->prof_pool.push_back(a);
+    X->prof_pool.push_back(b);
+    return e;
 }
-ProfHookGuard::ProfHookGuard(Ctx& X) : prev(g_prof_hook)
+
+GlueProfGuard::GlueProfGuard(Ctx& X) : prev(g_prof_ctx)
 {
-    if (X.profiling) g_prof_hook = ProfHook{&X, prof_hook_begin, prof_hook_end};
+    if (X.profiling) g_prof_ctx = &X;
 }
-ProfHookGuard::~ProfHookGuard() { g_prof_hook = prev; }
+GlueProfGuard::~GlueProfGuard() { g_prof_ctx = prev; }
 
 hipEvent_t Ctx::prof_get_event()
 {
@@ -1719,9 +1668,12 @@ int p2p_ctx_create(int device, int max_batch, p2p_ctx** out)
     HIP_TRY(hipGetDeviceCount(&n));
     if (device < 0 || device >= n) { set_error("p2p_ctx_create: device %d out of range (%d devices)", device, n); return P2P_ERR_INVALID_ARG; }
     HIP_TRY(hipSetDevice(device));
+    int n_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
     Ctx* c = new Ctx();
     c->device = device;
     c->max_batch = max_batch;
+    c->n_cu = n_cu > 0 ? n_cu : 256;
     hipError_t e;
 #ifdef P2P_TIMING_SWITCHES
     c->dev_part = getenv("P2P_DEV_PART") ? atoi(getenv("P2P_DEV_PART")) : 0;

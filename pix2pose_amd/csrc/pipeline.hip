@@ -1913,7 +1913,7 @@ int p2p_est_pose_submit(p2p_ctx* ctx, const p2p_object* objects, int n_objects, 
         return P2P_ERR_INVALID_ARG;
     }
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ProfHookGuard prof_guard(*c);
+    GlueProfGuard prof_guard(*c);
     HIP_TRY(hipSetDevice(c->device));
     p2p_est_pose_opts o;
     memset(&o, 0, sizeof(o));
@@ -1925,7 +1925,7 @@ int p2p_est_pose_collect(p2p_ctx* ctx, int ticket, p2p_pose* poses)
 {
     if (!ctx || !poses) { set_error("p2p_est_pose_collect: bad arguments"); return P2P_ERR_INVALID_ARG; }
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ProfHookGuard prof_guard(*c);
+    GlueProfGuard prof_guard(*c);
     HIP_TRY(hipSetDevice(c->device));
     return collect_est_pose(*c, ticket, poses);
 }
@@ -1935,7 +1935,7 @@ int p2p_est_pose_collect_gathered(p2p_ctx* ctx, p2p_comm* comm, int ticket, p2p_
     // (argument errors are local: nothing was enqueued and the caller's peers are its own to unblock; poses may be null for an empty shard)
     if (!ctx || !comm || !gathered || n_max < 1 || (!poses && ticket != P2P_TICKET_NONE)) { set_error("p2p_est_pose_collect_gathered: bad arguments"); return P2P_ERR_INVALID_ARG; }
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ProfHookGuard prof_guard(*c);
+    GlueProfGuard prof_guard(*c);
     HIP_TRY(hipSetDevice(c->device));
     return collect_est_pose(*c, ticket, poses, reinterpret_cast<Comm*>(comm), n_max, gathered);
 }
@@ -2012,7 +2012,7 @@ int p2p_est_pose_batch(p2p_ctx* ctx, const p2p_object* objects, int n_objects, c
     }
     if (n_dets == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ProfHookGuard prof_guard(*c);
+    GlueProfGuard prof_guard(*c);
     HIP_TRY(hipSetDevice(c->device));
     p2p_est_pose_opts o;
     memset(&o, 0, sizeof(o));
@@ -2034,7 +2034,7 @@ int p2p_pnp_ransac_batch(p2p_ctx* ctx, const double* camK, const double* obj_pts
     }
     if (n_problems == 0) return P2P_OK;
     Ctx* c = reinterpret_cast<Ctx*>(ctx);
-    ProfHookGuard prof_guard(*c);
+    GlueProfGuard prof_guard(*c);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const int N = offsets[n_problems];

@@ -438,16 +438,9 @@ hipError_t launch_wino_input(const WinoParams& p, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_wino_gemm(const WinoParams& p, hipStream_t s)
+hipError_t launch_wino_gemm(const WinoParams& p, int n_cu, hipStream_t s)
 {
     // persistent: one workgroup per CU (the kernel's LDS image admits no second one) walks the tiles
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipGetLastError();
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     if (p.ksplit > 1 && ((p.Cin >> 4) % (2 * p.ksplit) || !p.partial || p.n_groups > 1)) return hipErrorInvalidValue;      // even slice ranges; one object
     const int tiles = wino_gemm_grid(p);
     const int grid = tiles < n_cu ? tiles : n_cu;

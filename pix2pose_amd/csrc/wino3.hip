@@ -445,16 +445,9 @@ hipError_t launch_wino3_input(const Wino3Params& p, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_wino3_gemm(const Wino3Params& p, hipStream_t s)
+hipError_t launch_wino3_gemm(const Wino3Params& p, int n_cu, hipStream_t s)
 {
     // persistent: the workgroups of a full chip walk the tiles; the grid is kept a multiple of the tiles of one patch (the phase rotation counts on it)
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipGetLastError();
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
 #ifdef P2P_W3_NU1
     constexpr int NU = 1;                            // A/B builds: 6-wave workgroups, two per CU -- measured 9 % slower (tools/experiments/README.md)
 #else

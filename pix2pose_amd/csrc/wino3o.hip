@@ -391,15 +391,8 @@ hipError_t launch_wino3o_input(const Wino3oParams& p, int mode, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_wino3o_gemm(const Wino3oParams& p, int mode, hipStream_t s)
+hipError_t launch_wino3o_gemm(const Wino3oParams& p, int mode, int n_cu, hipStream_t s)
 {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipGetLastError();
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     const int g4 = mode == 0 ? 4 * (p.Cout / 64) : (p.Cout / 64) * p.ksplit;
     const int tiles = wino3o_units(p) * g4;
     int grid = tiles < n_cu ? tiles : n_cu / g4 * g4;
