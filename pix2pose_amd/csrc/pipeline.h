@@ -170,7 +170,7 @@ struct Slot {
     DevBuf crange;                      // CandRange per candidate
     DevBuf sacc;                        // few detections: global accumulators of the segmented stage-1 reductions (self-clearing)
     int sacc_n = 0;
-    DevBuf crec, cseg;                  // few candidates: per-pixel records and per-segment counts of the two-launch correspondence build
+    DevBuf crec, cseg;                  // per-pixel records and per-segment counts of the two-launch correspondence build
     DevBuf aa_items, aa_cv, aa_cv_tmp, aa_bk, aa_bk_tmp;   // anti-aliased resizes: descriptors, canvases, 128x128 planes
     DevBuf keepf;                       // generation 2: filtered bool keep masks
     DevBuf mask, pred, dmask, mstat;    // optional outputs of the batch (valid_mask_full, img_pred_f, detector masks, IoU sums)
@@ -192,6 +192,7 @@ struct Slot {
     bool stage2_pending = false;        // stage-2 inputs are built, the stage-2 generator pass and the tail are not enqueued yet
     int tail_cap = 0;                   // network inputs of a following batch that fit behind this batch's stage-2 inputs
     int max_side = 0;
+    bool glue128 = false;               // more than a handful of detections, all of them 128-px stage-1 crops, no anti-aliasing
     AaPtrs aa = {nullptr, nullptr, nullptr, nullptr};
     std::vector<int> img_hw, img_w;     // H*W and W of each detection's frame (sorted order)
     long long cmask_stride = 0, cpred_stride = 0;   // bytes per detection of the compact mask / image landing buffers

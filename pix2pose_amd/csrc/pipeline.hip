@@ -18,6 +18,15 @@
 
 #pragma clang fp contract(off)
 
+// threads per workgroup of the one-workgroup-per-detection / per-candidate kernels when there are more than 64 of them (at 256 detections:
+// 256 threads were 4 waves per CU in stage1_stats_kernel; 512 measured faster than both 256 and 1024 for all three kernels)
+#ifndef P2P_STATS_NT
+#define P2P_STATS_NT 512
+#endif
+#ifndef P2P_CAND_NT
+#define P2P_CAND_NT 512
+#endif
+
 namespace p2p {
 
 int DevBuf::reserve(size_t bytes)
@@ -208,12 +217,10 @@ __device__ inline bool non_gray_at(const float* y4)   // np.linalg.norm(decode, 
 // ------------------------------------------------------------------------------------------
 // K1: stage-1 network inputs  (recognition.py:75-82)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stage1_input_kernel(const DetInfo* __restrict__ dets, float* __restrict__ x1, AaPtrs aa)
+// one output pixel, any crop side (the general path)
+__device__ inline void stage1_input_px(const DetInfo& D, int d, int pix, float* __restrict__ x1, const AaPtrs& aa)
 {
-    const int d = blockIdx.x >> 6;
-    const int pix = ((blockIdx.x & 63) << 8) | threadIdx.x;
     const int oy = pix >> 7, ox = pix & 127;
-    const DetInfo& D = dets[d];
     float* out = x1 + ((size_t)d * 16384 + pix) * 3;
     if (!D.ok1) { out[0] = out[1] = out[2] = 0.f; return; }
     const Boxes& b = D.b1;
@@ -233,6 +240,73 @@ __global__ __launch_bounds__(256) void stage1_input_kernel(const DetInfo* __rest
             }
         out[ch] = (float)lerp2(v[0][0], v[0][1], v[1][0], v[1][1], tr.d, tc.d);
     }
+}
+
+// The three channels of FOUR neighbouring pixels of one frame row, (pixel - 128) / 128 as float32, where `m` bit j says pixel x + j is wanted
+// (0.f elsewhere; pixels that are not wanted are not read).  Equal to (float)lerp2(frame_px(.), 0, 0, 0, 0, 0) of the general path at an
+// identity resize: with d = 0 on both axes lerp2 is (1 - 0) * ((1 - 0) * v + 0 * 0) + 0 * ((1 - 0) * 0 + 0 * 0) = (v + 0) + 0 = v for
+// every v but -0.0 (which gives +0.0), and v = (p - 128) / 128 is never -0.0 (p - 128 == 0 only for p == 128: +0.0 in round-to-nearest),
+// so the result is (float)v.  A uint8 pixel: p - 128 is an integer in [-128, 127] and the division by 2^7 is exact in float32 as in
+// float64, so the float32 expression below IS (float)(double)v; a float32 pixel keeps the float64 expression of frame_px.
+__device__ inline void frame_quad(const DetInfo& D, int y, int x, unsigned m, float o[12])
+{
+    const long long e = ((long long)y * D.W + x) * 3;      // x < 0 where the run starts left of the window: those pixels are not wanted
+    if (D.img_f32) {
+        const float* f = reinterpret_cast<const float*>(D.img) + e;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o[k] = ((m >> (k / 3)) & 1u) ? (float)(((double)f[k] - 128.0) / 128.0) : 0.f;
+        return;
+    }
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(D.img) + e;
+    unsigned char px[12];
+    if (m == 15u) __builtin_memcpy(px, b, 12);      // 12 contiguous bytes of the frame row
+    else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) px[k] = ((m >> (k / 3)) & 1u) ? b[k] : (unsigned char)128;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o[k] = ((m >> (k / 3)) & 1u) ? ((float)px[k] - 128.0f) * 0.0078125f : 0.f;
+}
+
+__device__ inline void store_quad(float* out, const float o[12])      // 4 pixels x 3 channels = 48 contiguous, 16-byte aligned bytes
+{
+    float4* q = reinterpret_cast<float4*>(out);
+    q[0] = make_float4(o[0], o[1], o[2], o[3]);
+    q[1] = make_float4(o[4], o[5], o[6], o[7]);
+    q[2] = make_float4(o[8], o[9], o[10], o[11]);
+}
+
+// QUAD = false: one thread per output pixel (grid n * 64).  QUAD = true (grid n * 16; the host launches it for batches of 128-px crops
+// without anti-aliasing): one thread per run of four pixels of an output row = three 16-byte stores; a detection whose resize is not the
+// identity (decided per workgroup) takes the general path pixel by pixel.
+template <bool QUAD>
+__global__ __launch_bounds__(256) void stage1_input_kernel(const DetInfo* __restrict__ dets, float* __restrict__ x1, AaPtrs aa)
+{
+    if (!QUAD) {
+        const int d = blockIdx.x >> 6;
+        stage1_input_px(dets[d], d, ((blockIdx.x & 63) << 8) | threadIdx.x, x1, aa);
+        return;
+    }
+    const int d = blockIdx.x >> 4;
+    const int pix = (((blockIdx.x & 15) << 8) | threadIdx.x) << 2;
+    const DetInfo& D = dets[d];
+    const Boxes& b = D.b1;
+    const bool ident = D.ok1 && b.v2_ori - b.v1_ori == 128 && b.u2_ori - b.u1_ori == 128 && !(aa.k0 && aa.k0[d].radius > 0);
+    if (!ident) {
+        for (int j = 0; j < 4; ++j) stage1_input_px(D, d, pix + j, x1, aa);
+        return;
+    }
+    // identity resize: output pixel (oy, ox) is canvas pixel (oy, ox) (reflect_idx(o, 128) == o for 0 <= o < 128)
+    const int oy = pix >> 7, ox = pix & 127;
+    unsigned m = 0;
+    if (oy >= b.vv1 && oy < b.vv2)
+        for (int j = 0; j < 4; ++j)
+            if (ox + j >= b.uu1 && ox + j < b.uu2) m |= 1u << j;
+    float o[12];
+    if (m) frame_quad(D, b.v1 + oy - b.vv1, b.u1 + ox - b.uu1, m, o);
+    else
+        for (int k = 0; k < 12; ++k) o[k] = 0.f;
+    store_quad(x1 + ((size_t)d * 16384 + pix) * 3, o);
 }
 
 // stage-2 geometry from the reductions of one detection (recognition.py:96-110)
@@ -270,7 +344,7 @@ __device__ inline void stage1_finalize(const DetInfo& D, int s_n, int s_minv, in
 // ------------------------------------------------------------------------------------------
 // K3: stage-1 reductions + stage-2 geometry  (recognition.py:89-110)
 // ------------------------------------------------------------------------------------------
-// (blockDim.x = 256, or 1024 for a handful of detections: one workgroup per detection walks 16 384 pixels, and with one detection at a
+// (blockDim.x = 512, or 1024 for a handful of detections: one workgroup per detection walks 16 384 pixels, and with one detection at a
 // time -- the reference's caller -- its 64 trips were 50 us of the call)
 __global__ __launch_bounds__(1024) void stage1_stats_kernel(const DetInfo* __restrict__ dets, const float* __restrict__ y1,
                                                             Stage1* __restrict__ s1)
@@ -287,16 +361,24 @@ __global__ __launch_bounds__(1024) void stage1_stats_kernel(const DetInfo* __res
 #pragma unroll
     for (int k = 0; k < MAX_TH; ++k) keep[k] = 0;
     const float* y = y1 + (size_t)d * 16384 * 4;
-    for (int p = tid; p < 16384; p += blockDim.x) {
-        const float4 q = reinterpret_cast<const float4*>(y)[p];
-        const float v4[4] = {q.x, q.y, q.z, q.w};
-        if (!non_gray_at(v4)) continue;
-        const int v = p >> 7, u = p & 127;
-        ++n; sv += v; su += u;
-        minv = min(minv, v); maxv = max(maxv, v); minu = min(minu, u); maxu = max(maxu, u);
+    const int nt = blockDim.x;      // 256, 512 or 1024: 16 384 is a multiple of 4 * nt
+    for (int p0 = tid; p0 < 16384; p0 += 4 * nt) {
+        float4 q4[4];               // four 16-byte loads in flight (a trip that waits for its own load is what bounded this kernel)
 #pragma unroll
-        for (int k = 0; k < MAX_TH; ++k)
-            if (k < D.n_th && q.w < D.th_o[k]) ++keep[k];
+        for (int j = 0; j < 4; ++j) q4[j] = reinterpret_cast<const float4*>(y)[p0 + j * nt];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4 q = q4[j];
+            const int p = p0 + j * nt;
+            const float v4[4] = {q.x, q.y, q.z, q.w};
+            if (!non_gray_at(v4)) continue;
+            const int v = p >> 7, u = p & 127;
+            ++n; sv += v; su += u;
+            minv = min(minv, v); maxv = max(maxv, v); minu = min(minu, u); maxu = max(maxu, u);
+#pragma unroll
+            for (int k = 0; k < MAX_TH; ++k)
+                if (k < D.n_th && q.w < D.th_o[k]) ++keep[k];
+        }
     }
     atomicAdd(&s_n, n); atomicAdd(&s_sv, sv); atomicAdd(&s_su, su);
     atomicMin(&s_minv, minv); atomicMin(&s_minu, minu); atomicMax(&s_maxv, maxv); atomicMax(&s_maxu, maxu);
@@ -466,6 +548,79 @@ __global__ __launch_bounds__(256) void stage2_input_kernel(const DetInfo* __rest
     }
 }
 
+// The same for batches in which every usable stage-1 crop is 128 px and nothing is anti-aliased (Slot::glue128, decided on the host: no
+// filtered canvas or keep mask exists, and a detection with another side is not usable -- ok1 == 0, no live slot, zeros): one thread per
+// output pixel of ALL slots of a detection (grid n * 64).  The slots share the stage-2 box, hence the taps, the canvas positions, the frame pixels and the y1 records
+// behind them: those are evaluated once, and only the keep decision (th_o / kmin / kmax of the slot) and the interpolation of the kept
+// values are per slot.  With a 128-px stage-1 square (checked per workgroup) keep_ori_at's warp of the keep mask is the identity: its one
+// live tap is the y1 record at (y - v1_ori, x - u1_ori), and lerp2(k, 0, 0, 0, 0, 0) = (1 - 0) * ((1 - 0) * k + 0 * 0) + 0 * (...) = k for
+// k in {0.0, 1.0}, so keep = clip_warp(k, kmin, kmax, 0.0) > 0.9 -- the same comparison on the same value.  The stage-2 resize itself
+// (side <= 128 up to 128) keeps the general path's expressions: axis_tap, reflect_idx, P2P_TAP_LIVE, frame_px, lerp2, in that order.
+__global__ __launch_bounds__(256) void stage2_input_kernel_slots(const DetInfo* __restrict__ dets, const Stage1* __restrict__ s1,
+                                                                 const float* __restrict__ y1, int K, float* __restrict__ x2)
+{
+    const int d = blockIdx.x >> 6;
+    const int pix = ((blockIdx.x & 63) << 8) | threadIdx.x;
+    const DetInfo& D = dets[d];
+    const Stage1& S = s1[d];
+    const Boxes& b = S.b2;
+    const Boxes& b1 = D.b1;
+    bool any_on = false;      // a live slot: the detection is usable, hence (glue128) its stage-1 square is 128 x 128
+    if (b1.v2_ori - b1.v1_ori == 128 && b1.u2_ori - b1.u1_ori == 128)
+        for (int slot = 0; slot < K; ++slot) any_on = any_on || (slot < D.n_th && S.valid2[slot]);
+    // -- what the slots share: the four taps' canvas positions, frame pixels and y1 records
+    const int oy = pix >> 7, ox = pix & 127;
+    const int S2 = b.v2_ori - b.v1_ori, S2w = b.u2_ori - b.u1_ori;
+    const Tap tr = axis_tap(oy, S2, 128), tc = axis_tap(ox, S2w, 128);
+    const int r[2] = {reflect_idx(tr.i0, S2), reflect_idx(tr.i1, S2)};
+    const int c[2] = {reflect_idx(tc.i0, S2w), reflect_idx(tc.i1, S2w)};
+    bool in[2][2], ng[2][2];
+    float prob[2][2];
+    double px[2][2][3];
+    for (int a = 0; a < 2; ++a)
+        for (int e = 0; e < 2; ++e) {
+            in[a][e] = false; ng[a][e] = false; prob[a][e] = 0.f;
+            px[a][e][0] = px[a][e][1] = px[a][e][2] = 0.0;
+            if (!any_on || !P2P_TAP_LIVE(a, e, tr, tc)) continue;
+            // stage2_fg: inside the paste window of the stage-2 square and inside the clipped stage-1 crop (bg_full is True outside it)
+            if (!(r[a] >= b.vv1 && r[a] < b.vv2 && c[e] >= b.uu1 && c[e] < b.uu2)) continue;
+            const int y = b.v1 + r[a] - b.vv1, x = b.u1 + c[e] - b.uu1;
+            if (!(y >= b1.v1 && y < b1.v2 && x >= b1.u1 && x < b1.u2)) continue;
+            in[a][e] = true;
+            const int kr = y - b1.v1_ori, kc = x - b1.u1_ori;      // keep_ori_at's one live tap
+            if (kr >= 0 && kr < 128 && kc >= 0 && kc < 128) {
+                const float4 q = reinterpret_cast<const float4*>(y1 + (size_t)d * 16384 * 4)[kr * 128 + kc];
+                const float v4[4] = {q.x, q.y, q.z, q.w};
+                ng[a][e] = non_gray_at(v4);
+                prob[a][e] = q.w;
+            }
+            for (int ch = 0; ch < 3; ++ch) px[a][e][ch] = frame_px(D, y, x, ch);
+        }
+    // -- per slot: keep decision, interpolation, store
+    for (int slot = 0; slot < K; ++slot) {
+        float o[3] = {0.f, 0.f, 0.f};
+        if (any_on && slot < D.n_th && S.valid2[slot]) {
+            bool fg[2][2];
+            for (int a = 0; a < 2; ++a)
+                for (int e = 0; e < 2; ++e) {
+                    const double k = (ng[a][e] && prob[a][e] < D.th_o[slot]) ? 1.0 : 0.0;
+                    fg[a][e] = in[a][e] && clip_warp(k, S.kmin[slot], S.kmax[slot], 0.0) > 0.9;
+                }
+            // no kept tap (background: more than half of a crop): lerp2(0, 0, 0, 0, dr, dc) with 0 <= dr, dc < 1 is a sum of products
+            // +0.0 * non-negative = +0.0, so the output is the +0.f that o already holds
+            if (fg[0][0] || fg[0][1] || fg[1][0] || fg[1][1])
+                for (int ch = 0; ch < 3; ++ch) {
+                    double v[2][2];
+                    for (int a = 0; a < 2; ++a)
+                        for (int e = 0; e < 2; ++e) v[a][e] = fg[a][e] ? px[a][e][ch] : 0.0;
+                    o[ch] = (float)lerp2(v[0][0], v[0][1], v[1][0], v[1][1], tr.d, tc.d);
+                }
+        }
+        float* out = x2 + ((size_t)(d * K + slot) * 16384 + pix) * 3;      // (through LDS as 16-byte stores: measured the same, not kept)
+        out[0] = o[0]; out[1] = o[1]; out[2] = o[2];
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // per-pixel evaluation of one candidate at crop resolution  (recognition.py:134-154, 196-204)
 // ------------------------------------------------------------------------------------------
@@ -624,12 +779,20 @@ __global__ __launch_bounds__(1024) void cand_range_kernel(const float* __restric
     __shared__ double s_v[16][6];
     const float* y2c = y2 + (size_t)blockIdx.x * 16384 * 4;
     double v[6] = {1e300, -1e300, 1e300, -1e300, 1e300, -1e300};
-    for (int p = threadIdx.x; p < 16384; p += blockDim.x) {
-        double prob, ng, pred[3];
-        cand_raw(y2c + (size_t)p * 4, &prob, &ng, pred);
-        v[0] = fmin(v[0], prob); v[1] = fmax(v[1], prob);
-        for (int ch = 0; ch < 3; ++ch) { v[2] = fmin(v[2], pred[ch]); v[3] = fmax(v[3], pred[ch]); }
-        v[4] = fmin(v[4], ng); v[5] = fmax(v[5], ng);
+    const int nt = blockDim.x;      // 256, 512 or 1024: 16 384 is a multiple of 4 * nt
+    for (int p0 = threadIdx.x; p0 < 16384; p0 += 4 * nt) {
+        float4 q4[4];               // four 16-byte loads in flight; the pixels are then taken in the order of the one-by-one loop
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q4[j] = reinterpret_cast<const float4*>(y2c)[p0 + j * nt];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float q[4] = {q4[j].x, q4[j].y, q4[j].z, q4[j].w};
+            double prob, ng, pred[3];
+            cand_raw(q, &prob, &ng, pred);
+            v[0] = fmin(v[0], prob); v[1] = fmax(v[1], prob);
+            for (int ch = 0; ch < 3; ++ch) { v[2] = fmin(v[2], pred[ch]); v[3] = fmax(v[3], pred[ch]); }
+            v[4] = fmin(v[4], ng); v[5] = fmax(v[5], ng);
+        }
     }
     for (int o = 32; o > 0; o >>= 1)
         for (int k = 0; k < 6; ++k) {
@@ -657,7 +820,7 @@ __global__ __launch_bounds__(1024) void cand_corr_kernel(const DetInfo* __restri
                                                          const CandRange* __restrict__ crange, AaPtrs aa)
 {
     __shared__ int s_wave[16];
-    const int NT = blockDim.x, n_waves = NT >> 6;      // 256 threads, or 1024 for a handful of candidates (a 128-px candidate = 64 trips of 256)
+    const int NT = blockDim.x, n_waves = NT >> 6;      // 512 threads, or 1024 for a handful of candidates (a 128-px candidate = 32 trips of 512)
     __shared__ int s_ng;
     __shared__ unsigned long long s_sv, s_su;
     const int cand = blockIdx.x;
@@ -735,10 +898,12 @@ __global__ __launch_bounds__(1024) void cand_corr_kernel(const DetInfo* __restri
     }
 }
 
-// The same work for a HANDFUL of candidates (one detection at a time: three), as two launches over CORR_SEG pixel segments per candidate:
-// one workgroup per candidate spent 75 us walking its 16 384 pixels (the per-pixel evaluation is ~300 fp64 instructions); eight
-// segments on eight CUs evaluate them at once and leave a 4-byte record per pixel, then the compaction -- which needs the counts of
-// the segments before it, hence the second launch -- writes the correspondences in the same row-major order.
+// The same work as two launches over CORR_SEG pixel segments per candidate -- the route every batch takes (cand_corr_kernel above stays as
+// its one-launch twin behind the development switch P2P_CORR_SPLIT=0).  One workgroup per candidate spends its time in ~300 fp64
+// instructions per pixel between two barriers per 256 pixels: 75 us for the three candidates of a single detection, and 227 us for the 768
+// of a 256-detection step (three 8-wave workgroups per CU), where the two launches take 111 + 47 us (profiles/glue_after.txt).  Eight
+// segments per candidate evaluate barrier-free at full occupancy and leave a 4-byte record per pixel, then the compaction -- which needs
+// the counts of the segments before it, hence the second launch -- writes the correspondences in the same row-major order.
 constexpr int CORR_SEG = 8;
 struct CorrSeg { int n_valid, n_ng; unsigned long long sv, su; };
 
@@ -1384,6 +1549,7 @@ static int enqueue_front(Ctx& X, Pipeline& P, Slot& SL, hipStream_t st, const p2
     hd.resize(n);
     long long corr_total = 0, cv_total = 0;
     int max_side = 0;
+    bool all128 = true;
     const bool use_aa = SL.use_aa;
     for (int i = 0; i < n; ++i) {
         const p2p_detection& dt = dets[perm[i]];
@@ -1417,6 +1583,7 @@ static int enqueue_front(Ctx& X, Pipeline& P, Slot& SL, hipStream_t st, const p2
             cv_total += (long long)(1 + K) * D.corr_cap * 3;
         }
         if (D.ok1) max_side = std::max(max_side, (int)side);
+        if (D.ok1 && side != 128) all128 = false;
     }
     // -- frames.  Host frames (the reference's boundary: est_pose takes a numpy frame, recognition.py:70): only the rows some detection's
     // stage-1 crop covers are ever read (the stage-2 canvas is zero outside the stage-1 crop, recognition.py:105-106), so only those rows
@@ -1491,11 +1658,9 @@ static int enqueue_front(Ctx& X, Pipeline& P, Slot& SL, hipStream_t st, const p2
     if ((rc = SL.y2.reserve(sizeof(float) * 16384 * 4 * ((size_t)n * K + SL.tail_cap)))) return rc;
     if ((rc = SL.corr.reserve(sizeof(float) * (size_t)std::max<long long>(corr_total, 1)))) return rc;
     if ((rc = SL.crange.reserve(sizeof(CandRange) * (size_t)n * K))) return rc;
-    // two-launch correspondence build (cand_eval_kernel): a handful of candidates, or crops large enough that one workgroup per candidate
-    // leaves the launch waiting for its largest member
-    const bool corr_seg = n * K <= 16 || max_side > 192;
-    if (corr_seg && ((rc = SL.crec.reserve(sizeof(unsigned) * (size_t)std::max<long long>(corr_total / 5, 1))) ||
-                        (rc = SL.cseg.reserve(sizeof(CorrSeg) * CORR_SEG * (size_t)n * K)))) return rc;
+    // two-launch correspondence build (cand_eval_kernel): per-pixel records and per-segment counts
+    if ((rc = SL.crec.reserve(sizeof(unsigned) * (size_t)std::max<long long>(corr_total / 5, 1))) ||
+        (rc = SL.cseg.reserve(sizeof(CorrSeg) * CORR_SEG * (size_t)n * K))) return rc;
     SL.aa = {nullptr, nullptr, nullptr, nullptr};
     AaBufs aab = {nullptr, nullptr, nullptr, nullptr};
     AaTable aat;
@@ -1548,7 +1713,13 @@ static int enqueue_front(Ctx& X, Pipeline& P, Slot& SL, hipStream_t st, const p2
         HIP_TRY(hipGetLastError());
         HIP_TRY(launch_aa_filter(SL.aa.k0, n, max_side * max_side * 3, st));
     }
-    hipLaunchKernelGGL(stage1_input_kernel, dim3(n * 64), dim3(256), 0, st, d_det, x1_dst ? x1_dst : SL.x1.as<float>(), SL.aa);
+    // every usable stage-1 crop is 128 px, nothing is anti-aliased, more than a handful of detections: stage1_input_kernel<true> (four pixels
+    // per thread) and stage2_input_kernel_slots (the slots of a detection share a thread)
+    SL.glue128 = all128 && !use_aa && n > 16;
+    if (SL.glue128)
+        hipLaunchKernelGGL(stage1_input_kernel<true>, dim3(n * 16), dim3(256), 0, st, d_det, x1_dst ? x1_dst : SL.x1.as<float>(), SL.aa);
+    else
+        hipLaunchKernelGGL(stage1_input_kernel<false>, dim3(n * 64), dim3(256), 0, st, d_det, x1_dst ? x1_dst : SL.x1.as<float>(), SL.aa);
     HIP_TRY(hipGetLastError());
     return P2P_OK;
 }
@@ -1569,7 +1740,7 @@ static int enqueue_mid(Ctx& X, Slot& SL, hipStream_t st, float* y1)
         }
         hipLaunchKernelGGL(stage1_stats_seg_kernel, dim3(STATS_SEG, n), dim3(256), 0, st, d_det, y1, d_s1, SL.sacc.as<StatsAcc>());
     } else
-        hipLaunchKernelGGL(stage1_stats_kernel, dim3(n), dim3(n <= 64 ? 1024 : 256), 0, st, d_det, y1, d_s1);
+        hipLaunchKernelGGL(stage1_stats_kernel, dim3(n), dim3(n <= 64 ? 1024 : P2P_STATS_NT), 0, st, d_det, y1, d_s1);
     HIP_TRY(hipGetLastError());
     if (SL.use_aa) {      // anti-aliased stage-2 canvases (sides > 128; the bool keep masks of sides < 128 are not filtered, see aa_plan_kernel)
         AaTable aat;
@@ -1588,7 +1759,8 @@ static int enqueue_mid(Ctx& X, Slot& SL, hipStream_t st, float* y1)
     }
     {
         ProfScope ps(19, st);
-        hipLaunchKernelGGL(stage2_input_kernel, dim3(n * K * 64), dim3(256), 0, st, d_det, d_s1, y1, K, SL.x2.as<float>(), SL.aa);
+        if (SL.glue128) hipLaunchKernelGGL(stage2_input_kernel_slots, dim3(n * 64), dim3(256), 0, st, d_det, d_s1, y1, K, SL.x2.as<float>());
+        else hipLaunchKernelGGL(stage2_input_kernel, dim3(n * K * 64), dim3(256), 0, st, d_det, d_s1, y1, K, SL.x2.as<float>(), SL.aa);
     }
     HIP_TRY(hipGetLastError());
     return P2P_OK;
@@ -1609,7 +1781,7 @@ static int enqueue_tail(Pipeline& P, Slot& SL, hipStream_t st, bool async)
 
     // -- ranges of the back-resize inputs (clip=True), anti-aliased maps where the stage-2 side is < 128
     CandRange* d_cr = SL.crange.as<CandRange>();
-    const int glue_nt = n * K <= 64 ? 1024 : 256;      // per-candidate workgroups: wide when there are few of them
+    const int glue_nt = n * K <= 64 ? 1024 : P2P_CAND_NT;      // per-candidate workgroups: wide when there are few of them
     hipLaunchKernelGGL(cand_range_kernel, dim3(n * K), dim3(glue_nt), 0, st, y2, d_cr);
     HIP_TRY(hipGetLastError());
     if (SL.use_aa) {
@@ -1624,7 +1796,7 @@ static int enqueue_tail(Pipeline& P, Slot& SL, hipStream_t st, bool async)
     static const bool corr_split = dev_env("P2P_CORR_SPLIT") == nullptr || atoi(dev_env("P2P_CORR_SPLIT")) != 0;      // development switch (A/B)
     {
     ProfScope ps_corr(18, st);
-    if ((n * K <= 16 || SL.max_side > 192) && corr_split) {        // evaluate on CORR_SEG CUs per candidate, then compact (see cand_eval_kernel)
+    if (corr_split) {        // evaluate on CORR_SEG CUs per candidate, then compact (see cand_eval_kernel)
         hipLaunchKernelGGL(cand_eval_kernel, dim3(CORR_SEG, n * K), dim3(256), 0, st, d_det, d_s1, y2, K, SL.crec.as<unsigned>(), SL.cseg.as<CorrSeg>(), d_cr, aa);
         hipLaunchKernelGGL(cand_compact_kernel, dim3(CORR_SEG, n * K), dim3(256), 0, st, d_det, d_s1, K, SL.crec.as<unsigned>(), SL.cseg.as<CorrSeg>(),
                            SL.corr.as<float>(), SL.cand.as<CandStat>(), SL.probs.as<PnpProblem>());
