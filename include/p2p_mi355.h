@@ -622,6 +622,40 @@ P2P_API int p2p_rgbd_resolve(p2p_rgbd* h, int round, int n_images, const int* tg
                              const int* cand_off, const int* cand_obj, const int* cand_ref, const p2p_refine_result* host_records,
                              const unsigned char* host_masks, int n_records, int* roi_used, int* inst_pred, double* rows);
 
+/* ------------------------------------------------------------------------------------------
+ * XYZ-coloured renders (training targets, reference tools/2_2_render_pix2pose_training.py through rendering/renderer_xyz.py).
+ * csrc/depth.hip; DESIGN.md section 8.4.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Per-vertex colours of a mesh: rgb host u8 [n_verts][3] (the red, green, blue properties of a models_xyz PLY), stored as
+ * float32(c) / 255 like Model3D.load.  n_verts must equal the mesh's vertex count.  May be called again to replace the colours. */
+P2P_API int p2p_mesh_set_colors(p2p_mesh* mesh, const unsigned char* rgb, int n_verts);
+
+/* Colour z-buffer of the jobs of p2p_render_depth_batch (union_mask and img_idx unused): geometry, coverage, clipping and the depth
+ * value are that entry point's, bit for bit.  color: host float32 [n_jobs][height][width][3], channel order (x, y, z) = the PLY's
+ * (red, green, blue); the perspective-correct varying c = (sum b_i c_i / z_i) / (sum b_i / z_i) of the fragment that owns the pixel,
+ * fp64 without contraction, stored as float32; 0 where nothing is drawn.  The owner is the nearest fragment; among fragments of equal
+ * float32 depth the lowest triangle index (GL_LESS, triangles drawn in index order).  depth (may be null): host float32
+ * [n_jobs][height][width].  bbox (may be null): host int [n_jobs][4] = [min v, min u, max v, max u] of depth > 0, max inclusive
+ * (get_rendering's box), reduced on the device; [-1, -1, -1, -1] for an empty render.  A job's result is bit-identical alone or in
+ * a batch and from call to call.  A mesh without colours is P2P_ERR_INVALID_ARG. */
+P2P_API int p2p_render_xyz_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs,
+                                 int height, int width, float* color, float* depth, int* bbox);
+
+/* Training patches from colour renders (tools/2_2_render_pix2pose_training.py:168-184).  Job k: rgb[k] host u8 [height][width][3],
+ * its render color [k][height][width][3] / depth [k][height][width] / bbox [k][4] as p2p_render_xyz_batch returns them (host).  The
+ * patch is uint8 [h][w][6]: rgb with [128,128,128] where depth == 0, then xyz -- the colour as the reference reads it back from an
+ * 8-bit GL buffer and stores it: q = floor(c * 255 + 0.5), then uint8(float32(float32(q) / 255) * 255), which for some q is q - 1 --
+ * cropped to rows bbox[0]:bbox[2], columns bbox[1]:bbox[3] (the box's max is inclusive: the last covered row and column are left
+ * out, as in the reference).  When max(h, w) > 128 each half is resized on its own to int(h * s + 0.5) x int(w * s + 0.5),
+ * s = 128.0 / max(h, w), by skimage.transform.resize(order = 1) of generation resize_generation (p2p_est_pose_opts.
+ * resize_anti_aliasing's numbering: 0, 1 or 2, with that generation's default mode and anti-aliasing) acting on float32(x / 255);
+ * the result times 255 is truncated.  patches: host u8 [n_jobs][128][128][6], job k's patch in the
+ * top-left shapes[k][0] x shapes[k][1] corner with row stride 128 (the rest 0); shapes: host int [n_jobs][2].  A job whose render is
+ * empty (bbox[0] < 0) or whose box has a zero side reports (0, 0) and writes nothing: the caller skips it. */
+P2P_API int p2p_xyz_patch_batch(p2p_ctx* ctx, const unsigned char* const* rgb, const float* color, const float* depth, const int* bbox,
+                                int n_jobs, int height, int width, int resize_generation, unsigned char* patches, int* shapes);
+
 #ifdef __cplusplus
 }
 #endif

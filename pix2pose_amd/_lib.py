@@ -302,6 +302,9 @@ def lib():
     L.p2p_rgbd_refine.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), C.POINTER(ci), ci, C.POINTER(IcpParams),
                                   C.POINTER(RefineResult), vp, vp]
     L.p2p_rgbd_resolve.argtypes = [vp, ci, ci] + [vp] * 11 + [C.POINTER(RefineResult), vp, ci, vp, vp, vp]
+    L.p2p_mesh_set_colors.argtypes = [vp, vp, ci]
+    L.p2p_render_xyz_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci, vp, vp, vp]
+    L.p2p_xyz_patch_batch.argtypes = [vp, C.POINTER(vp), vp, vp, vp, ci, ci, ci, ci, vp, vp]
     _lib = L
     return L
 

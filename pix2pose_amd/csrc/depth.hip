@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "model.h"
@@ -18,6 +19,7 @@ struct p2p_mesh {
     int n_verts = 0, n_tris = 0;
     float* verts = nullptr;   // [n_verts][3] metres (float32, like Model3D.load(scale=0.001))
     int* tris = nullptr;      // [n_tris][3], every index checked against n_verts at creation
+    float* colors = nullptr;  // [n_verts][3] float32(c) / 255 (p2p_mesh_set_colors), null until set
 };
 
 namespace p2p {
@@ -26,6 +28,10 @@ namespace {
 
 constexpr double CLIP_NEAR = 0.01, CLIP_FAR = 10.0;      // Renderer.set_cam defaults (renderer_xyz.py:126)
 constexpr unsigned DEPTH_EMPTY = 0x7f800000u;            // +inf: above every finite depth in the atomicMin order of positive floats
+// Winner key of the colour path: (depth bits << 32) | triangle index, so atomicMin keeps the nearest fragment and, among fragments
+// of equal float32 depth, the lowest triangle index.  All ones (what a byte memset writes) is above every key of a drawn fragment.
+typedef unsigned long long WinnerKey;
+constexpr WinnerKey KEY_EMPTY = ~0ull;
 constexpr int RASTER_THREADS = 256, SCORE_THREADS = 256;
 
 // One job as the device sees it: the mesh's arrays, the pose in metres (unit quirk applied), the intrinsics.
@@ -35,6 +41,7 @@ struct RasterJob {
     int n_tris;
     double R[9], t[3];
     double fx, s, cx, fy, cy;
+    const float* colors;      // colour path only
 };
 
 // Edge function of a -> b at p, and the owner rule for a sample exactly on the edge: with the triangle ordered so that
@@ -87,8 +94,11 @@ __device__ __forceinline__ bool tri_setup(const RasterJob& J, int f, int H, int 
     return T.i0 <= T.i1 && T.j0 <= T.j1;
 }
 
-// One pixel centre of a set-up triangle: coverage with the tie rule, 1/z interpolation, far clip, atomicMin on the float bits.
-__device__ __forceinline__ void tri_pixel(const TriSetup& T, int i, int j, unsigned* zrow_base, int W)
+// One pixel centre of a set-up triangle: coverage with the tie rule, 1/z interpolation, far clip, atomicMin on the float bits
+// (Z = unsigned, the depth path) or on the winner key of triangle f (Z = WinnerKey, the colour path): one body, so both paths cover
+// the same centres with the same depth.
+template <typename Z>
+__device__ __forceinline__ void tri_pixel(const TriSetup& T, int i, int j, Z* zrow_base, int W, int f)
 {
     const double pu = i + 0.5, pv = j + 0.5;
     const double e0 = edge_fn(T.u[1], T.v[1], T.u[2], T.v[2], pu, pv);
@@ -100,13 +110,15 @@ __device__ __forceinline__ void tri_pixel(const TriSetup& T, int i, int j, unsig
     const double iz = (e0 / T.A) / T.z[0] + (e1 / T.A) / T.z[1] + (e2 / T.A) / T.z[2];
     const double d = 1.0 / iz;
     if (!(d >= CLIP_NEAR && d <= CLIP_FAR)) return;
-    atomicMin(zrow_base + (size_t)j * W + i, __float_as_uint((float)d));
+    if constexpr (std::is_same<Z, WinnerKey>::value) atomicMin(zrow_base + (size_t)j * W + i, ((WinnerKey)__float_as_uint((float)d) << 32) | (unsigned)f);
+    else atomicMin(zrow_base + (size_t)j * W + i, __float_as_uint((float)d));
 }
 
 // Route 1: one thread per triangle (blockIdx.y = job) walks its pixel box when the box holds at most BIG_TRI_PIXELS centres;
 // larger triangles (near the camera, coarse meshes) are appended to `big` for route 2, so no thread walks a large box alone.
 constexpr int BIG_TRI_PIXELS = 1024;
-__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_kernel(const RasterJob* __restrict__ jobs, unsigned* __restrict__ zbuf,
+template <typename Z>
+__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_kernel(const RasterJob* __restrict__ jobs, Z* __restrict__ zbuf,
                                                                       int H, int W, int2* __restrict__ big, unsigned* __restrict__ n_big)
 {
     const RasterJob& J = jobs[blockIdx.y];
@@ -118,14 +130,15 @@ __global__ void __launch_bounds__(RASTER_THREADS) depth_raster_kernel(const Rast
         big[atomicAdd(n_big, 1u)] = make_int2((int)blockIdx.y, f);      // at most one entry per (job, triangle): within capacity
         return;
     }
-    unsigned* zb = zbuf + (size_t)blockIdx.y * H * W;
+    Z* zb = zbuf + (size_t)blockIdx.y * H * W;
     for (int j = T.j0; j <= T.j1; ++j)
-        for (int i = T.i0; i <= T.i1; ++i) tri_pixel(T, i, j, zb, W);
+        for (int i = T.i0; i <= T.i1; ++i) tri_pixel(T, i, j, zb, W, f);
 }
 
 // Route 2: one workgroup per large triangle, its threads striding over the pixel box.  The list order depends on scheduling;
 // the result does not (atomicMin), so both routes together stay deterministic.
-__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_big_kernel(const RasterJob* __restrict__ jobs, unsigned* __restrict__ zbuf,
+template <typename Z>
+__global__ void __launch_bounds__(RASTER_THREADS) depth_raster_big_kernel(const RasterJob* __restrict__ jobs, Z* __restrict__ zbuf,
                                                                           int H, int W, const int2* __restrict__ big,
                                                                           const unsigned* __restrict__ n_big)
 {
@@ -134,10 +147,10 @@ __global__ void __launch_bounds__(RASTER_THREADS) depth_raster_big_kernel(const 
         const int2 jf = big[e];
         TriSetup T;
         if (!tri_setup(jobs[jf.x], jf.y, H, W, T)) continue;     // same set-up as route 1: succeeds
-        unsigned* zb = zbuf + (size_t)jf.x * H * W;
+        Z* zb = zbuf + (size_t)jf.x * H * W;
         const int bw = T.i1 - T.i0 + 1;
         const int64_t npix = (int64_t)bw * (T.j1 - T.j0 + 1);
-        for (int64_t q = threadIdx.x; q < npix; q += RASTER_THREADS) tri_pixel(T, T.i0 + (int)(q % bw), T.j0 + (int)(q / bw), zb, W);
+        for (int64_t q = threadIdx.x; q < npix; q += RASTER_THREADS) tri_pixel(T, T.i0 + (int)(q % bw), T.j0 + (int)(q / bw), zb, W, jf.y);
     }
 }
 
@@ -145,6 +158,85 @@ __global__ void depth_finish_kernel(unsigned* __restrict__ zbuf, size_t n)
 {
     for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x)
         if (zbuf[k] == DEPTH_EMPTY) zbuf[k] = 0u;        // +0.0f
+}
+
+// Colour path, after both raster routes: one thread per pixel of job blockIdx.y reads the winner key once, sets the winning triangle
+// up again (the set-up of the raster routes: it succeeds and orders the vertices the same way) and evaluates the GL varying at the
+// centre, perspective-correct: c = (sum b_i c_i / z_i) / (sum b_i / z_i) with the screen-space barycentrics b_i = e_i / A of the
+// depth.  Nothing here depends on which route drew the triangle or on the order of the atomics.  The workgroup's 256 x 3 colour
+// floats go through LDS so that consecutive threads store consecutive floats; the box of depth > 0 is reduced per wave, per
+// workgroup, then with four atomics per workgroup that covers anything.
+constexpr int RESOLVE_THREADS = 256;
+__global__ void __launch_bounds__(RESOLVE_THREADS) xyz_resolve_kernel(const RasterJob* __restrict__ jobs, const WinnerKey* __restrict__ keys,
+                                                                      int H, int W, float* __restrict__ color, float* __restrict__ depth,
+                                                                      int* __restrict__ bbox)
+{
+    __shared__ float s_c[RESOLVE_THREADS * 3];
+    __shared__ int s_bb[RESOLVE_THREADS / 64][4];
+    const int job = blockIdx.y;
+    const int HW = H * W;
+    const int p0 = blockIdx.x * RESOLVE_THREADS;
+    const int p = p0 + threadIdx.x;
+    float c[3] = {0.f, 0.f, 0.f};
+    float d = 0.f;
+    int vlo = 0x7fffffff, ulo = 0x7fffffff, vhi = -1, uhi = -1;
+    if (p < HW) {
+        const WinnerKey key = keys[(size_t)job * HW + p];
+        const RasterJob& J = jobs[job];
+        const int f = (int)(unsigned)key;
+        TriSetup T;
+        // the set-up that drew the key succeeds again (same inputs, same code); were it not to, the pixel stays empty
+        if (key != KEY_EMPTY && tri_setup(J, f, H, W, T)) {
+            const int j = p / W, i = p - j * W;
+            d = __uint_as_float((unsigned)(key >> 32));
+            const double pu = i + 0.5, pv = j + 0.5;
+            const double b0 = edge_fn(T.u[1], T.v[1], T.u[2], T.v[2], pu, pv) / T.A;
+            const double b1 = edge_fn(T.u[2], T.v[2], T.u[0], T.v[0], pu, pv) / T.A;
+            const double b2 = edge_fn(T.u[0], T.v[0], T.u[1], T.v[1], pu, pv) / T.A;
+            const double iz = b0 / T.z[0] + b1 / T.z[1] + b2 / T.z[2];
+            // tri_setup swapped vertices 1 and 2 for a positive area: the colours follow
+            const float* c0 = J.colors + 3 * (size_t)J.tris[3 * (size_t)f];
+            const float* c1 = J.colors + 3 * (size_t)J.tris[3 * (size_t)f + 2];
+            const float* c2 = J.colors + 3 * (size_t)J.tris[3 * (size_t)f + 1];
+            for (int k = 0; k < 3; ++k)
+                c[k] = (float)(((b0 * (double)c0[k]) / T.z[0] + (b1 * (double)c1[k]) / T.z[1] + (b2 * (double)c2[k]) / T.z[2]) / iz);
+            if (d > 0.f) { vlo = vhi = j; ulo = uhi = i; }
+        }
+        if (depth) depth[(size_t)job * HW + p] = d;
+    }
+    s_c[threadIdx.x * 3 + 0] = c[0]; s_c[threadIdx.x * 3 + 1] = c[1]; s_c[threadIdx.x * 3 + 2] = c[2];
+    for (int o = 32; o > 0; o >>= 1) {
+        vlo = min(vlo, __shfl_down(vlo, o, 64)); ulo = min(ulo, __shfl_down(ulo, o, 64));
+        vhi = max(vhi, __shfl_down(vhi, o, 64)); uhi = max(uhi, __shfl_down(uhi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        int* b = s_bb[threadIdx.x >> 6];
+        b[0] = vlo; b[1] = ulo; b[2] = vhi; b[3] = uhi;
+    }
+    __syncthreads();
+    const int n_here = min(RESOLVE_THREADS, HW - p0) * 3;      // floats of this workgroup's pixels that exist
+    float* out = color + ((size_t)job * HW + p0) * 3;
+    for (int k = threadIdx.x; k < n_here; k += RESOLVE_THREADS) out[k] = s_c[k];
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < RESOLVE_THREADS / 64; ++w) {
+            vlo = min(vlo, s_bb[w][0]); ulo = min(ulo, s_bb[w][1]); vhi = max(vhi, s_bb[w][2]); uhi = max(uhi, s_bb[w][3]);
+        }
+        if (vhi >= 0) {
+            atomicMin(bbox + 4 * job + 0, vlo); atomicMin(bbox + 4 * job + 1, ulo);
+            atomicMax(bbox + 4 * job + 2, vhi); atomicMax(bbox + 4 * job + 3, uhi);
+        }
+    }
+}
+
+// bbox [n][4]: the neutral element before the resolve (FINISH = false), the [-1, -1, -1, -1] of an empty render after it
+template <bool FINISH>
+__global__ void xyz_bbox_kernel(int* __restrict__ bbox, int n_jobs)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_jobs) return;
+    int* b = bbox + 4 * j;
+    if (!FINISH) { b[0] = b[1] = 0x7fffffff; b[2] = b[3] = -1; }
+    else if (b[2] < 0) b[0] = b[1] = -1;
 }
 
 // One workgroup per job.  Thread k takes pixels k, k + 256, ...; its partial sums are combined by a fixed tree, so the result of a
@@ -213,8 +305,12 @@ int check_jobs(const char* who, const p2p_mesh* const* meshes, int n_meshes, con
     return P2P_OK;
 }
 
-// Renders every job into zbuf [n_jobs][H][W] (device, float bits), 0 where nothing is drawn.
-int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, unsigned* zbuf, DevBuf& djobs)
+namespace {
+
+// Both raster routes of every job into zbuf [n_jobs][H][W] (device): float bits under DEPTH_EMPTY (Z = unsigned) or winner keys
+// under KEY_EMPTY (Z = WinnerKey).  The job records stay at the front of djobs for the kernels that follow.
+template <typename Z>
+int raster_jobs(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, Z* zbuf, DevBuf& djobs)
 {
     hipStream_t st = X.stream;
     std::vector<RasterJob> rj(n_jobs);
@@ -227,7 +323,7 @@ int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* job
             return P2P_ERR_INVALID_ARG;
         }
         RasterJob& r = rj[j];
-        r.verts = M->verts; r.tris = M->tris; r.n_tris = M->n_tris;
+        r.verts = M->verts; r.tris = M->tris; r.n_tris = M->n_tris; r.colors = M->colors;
         for (int k = 0; k < 9; ++k) r.R[k] = J.R[k];
         double tm[3];
         for (int k = 0; k < 3; ++k) tm[k] = J.t[k] / 1000.0;            // icp3d.py: render_obj(..., tra_pred/1000, ...)
@@ -247,14 +343,27 @@ int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* job
     const size_t n = (size_t)n_jobs * H * W;
     HIP_TRY(hipMemcpyAsync(dj, rj.data(), sizeof(RasterJob) * n_jobs, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(n_big, 0, sizeof(unsigned), st));
-    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)zbuf, (int)DEPTH_EMPTY, n, st));
+    if constexpr (std::is_same<Z, WinnerKey>::value) HIP_TRY(hipMemsetAsync(zbuf, 0xff, n * sizeof(Z), st));      // KEY_EMPTY
+    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)zbuf, (int)DEPTH_EMPTY, n, st));
     if (max_tris > 0) {
         dim3 grid((max_tris + RASTER_THREADS - 1) / RASTER_THREADS, n_jobs);
-        depth_raster_kernel<<<grid, RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
+        depth_raster_kernel<Z><<<grid, RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
         HIP_TRY(hipGetLastError());
-        depth_raster_big_kernel<<<(unsigned)std::min<size_t>(cap, 1024), RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
+        depth_raster_big_kernel<Z><<<(unsigned)std::min<size_t>(cap, 1024), RASTER_THREADS, 0, st>>>(dj, zbuf, H, W, big, n_big);
         HIP_TRY(hipGetLastError());
     }
+    return P2P_OK;
+}
+
+}  // namespace
+
+// Renders every job into zbuf [n_jobs][H][W] (device, float bits), 0 where nothing is drawn.
+int render_into(Ctx& X, const p2p_mesh* const* meshes, const p2p_refine_job* jobs, int n_jobs, int H, int W, unsigned* zbuf, DevBuf& djobs)
+{
+    int rc;
+    if ((rc = raster_jobs(X, meshes, jobs, n_jobs, H, W, zbuf, djobs))) return rc;
+    hipStream_t st = X.stream;
+    const size_t n = (size_t)n_jobs * H * W;
     const int blocks = (int)std::min<size_t>((n + 255) / 256, 4096);
     depth_finish_kernel<<<blocks, 256, 0, st>>>(zbuf, n);
     HIP_TRY(hipGetLastError());
@@ -315,6 +424,7 @@ void p2p_mesh_destroy(p2p_mesh* mesh)
     (void)hipSetDevice(mesh->device);
     if (mesh->verts) (void)hipFree(mesh->verts);
     if (mesh->tris) (void)hipFree(mesh->tris);
+    if (mesh->colors) (void)hipFree(mesh->colors);
     delete mesh;
 }
 
@@ -335,6 +445,76 @@ int p2p_render_depth_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_me
     if ((rc = dz.reserve(n * 4)) || (rc = render_into(*c, meshes, jobs, n_jobs, height, width, dz.as<unsigned>(), dj))) return rc;
     HIP_TRY(hipMemcpyAsync(depth, dz.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return P2P_OK;
+}
+
+int p2p_mesh_set_colors(p2p_mesh* mesh, const unsigned char* rgb, int n_verts)
+{
+    if (!mesh || !rgb) {
+        set_error("p2p_mesh_set_colors: null %s", !mesh ? "mesh" : "colour array");
+        return P2P_ERR_INVALID_ARG;
+    }
+    if (n_verts != mesh->n_verts) {
+        set_error("p2p_mesh_set_colors: %d colours for a mesh of %d vertices", n_verts, mesh->n_verts);
+        return P2P_ERR_INVALID_ARG;
+    }
+    // Replacing the colours of a mesh reuses its array.  Every render entry point synchronises its stream before it returns, so no
+    // render of the calling thread is in flight here; a mesh shared with another thread's context must not be recoloured while that
+    // thread renders it (a p2p_mesh is no more thread-safe than a p2p_ctx).
+    HIP_TRY(hipSetDevice(mesh->device));
+    std::vector<float> c((size_t)n_verts * 3);
+    for (size_t k = 0; k < c.size(); ++k) c[k] = (float)rgb[k] / 255.0f;      // Model3D.load: float32 colours / 255
+    if (!mesh->colors) HIP_TRY(hipMalloc(&mesh->colors, c.size() * 4));
+    HIP_TRY(hipMemcpy(mesh->colors, c.data(), c.size() * 4, hipMemcpyHostToDevice));
+    return P2P_OK;
+}
+
+int p2p_render_xyz_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, int n_meshes, const p2p_refine_job* jobs, int n_jobs, int height,
+                         int width, float* color, float* depth, int* bbox)
+{
+    if (!ctx || n_jobs < 0 || (n_jobs > 0 && (!meshes || !jobs))) {
+        set_error("p2p_render_xyz_batch: bad arguments");
+        return P2P_ERR_INVALID_ARG;
+    }
+    if (n_jobs > 65535) {      // the raster and resolve grids carry the job in gridDim.y
+        set_error("p2p_render_xyz_batch: %d jobs in one call, at most 65535", n_jobs);
+        return P2P_ERR_INVALID_ARG;
+    }
+    if (n_jobs > 0 && !color) {
+        set_error("p2p_render_xyz_batch: the colour buffer is null");
+        return P2P_ERR_INVALID_ARG;
+    }
+    int rc;
+    if ((rc = check_jobs("p2p_render_xyz_batch", meshes, n_meshes, jobs, n_jobs, height, width, -1))) return rc;
+    for (int j = 0; j < n_jobs; ++j)
+        if (!meshes[jobs[j].mesh_idx]->colors) {
+            set_error("p2p_render_xyz_batch: job %d: mesh %d has no colours (p2p_mesh_set_colors)", j, jobs[j].mesh_idx);
+            return P2P_ERR_INVALID_ARG;
+        }
+    if (n_jobs == 0) return P2P_OK;
+    Ctx* c = reinterpret_cast<Ctx*>(ctx);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->pipe) c->pipe = new Pipeline();
+    Pipeline::XyzWork& Wk = c->pipe->xyz;
+    hipStream_t st = c->stream;
+    const size_t HW = (size_t)height * width, n = (size_t)n_jobs * HW;
+    if ((rc = Wk.key.reserve(n * sizeof(WinnerKey))) || (rc = Wk.color.reserve(n * 12)) || (rc = Wk.depth.reserve(n * 4)) ||
+        (rc = Wk.bbox.reserve(sizeof(int) * 4 * n_jobs)) ||
+        (rc = raster_jobs(*c, meshes, jobs, n_jobs, height, width, Wk.key.as<WinnerKey>(), Wk.jobs)))
+        return rc;
+    const int bb_blocks = (n_jobs + 255) / 256;
+    xyz_bbox_kernel<false><<<bb_blocks, 256, 0, st>>>(Wk.bbox.as<int>(), n_jobs);
+    HIP_TRY(hipGetLastError());
+    dim3 grid((unsigned)((HW + RESOLVE_THREADS - 1) / RESOLVE_THREADS), n_jobs);
+    xyz_resolve_kernel<<<grid, RESOLVE_THREADS, 0, st>>>(Wk.jobs.as<RasterJob>(), Wk.key.as<WinnerKey>(), height, width, Wk.color.as<float>(),
+                                                         Wk.depth.as<float>(), Wk.bbox.as<int>());
+    HIP_TRY(hipGetLastError());
+    xyz_bbox_kernel<true><<<bb_blocks, 256, 0, st>>>(Wk.bbox.as<int>(), n_jobs);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(color, Wk.color.p, n * 12, hipMemcpyDeviceToHost, st));
+    if (depth) HIP_TRY(hipMemcpyAsync(depth, Wk.depth.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (bbox) HIP_TRY(hipMemcpyAsync(bbox, Wk.bbox.p, sizeof(int) * 4 * n_jobs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return P2P_OK;
 }
 

@@ -71,6 +71,8 @@ struct AaTable {
 };
 int aa_table_get(int device, AaTable* out);          // builds + uploads once per device
 hipError_t launch_aa_filter(AaItem* items, int n_items, int max_elems, hipStream_t s);   // both axis passes + range
+int aa_weights_for_axis(int n_in, int n_out, std::vector<double>& w);      // one axis n_in -> n_out: radius, one-sided weights (centre first)
+hipError_t launch_aa_filter_axes(AaItem* rows, AaItem* cols, int n_items, int max_elems, hipStream_t s);   // per-axis radius / weights
 
 
 // Stage-1 reductions + stage-2 geometry, written by the device.
@@ -210,6 +212,9 @@ struct Pipeline {
     hipEvent_t corr_ready = nullptr;
     hipEvent_t frames_ready = nullptr;
     int next_ticket = 0;
+    // grow-only workspaces of p2p_render_xyz_batch (depth.hip): winner keys, colour and depth images, boxes, job records
+    struct XyzWork { DevBuf key, color, depth, bbox, jobs; } xyz;
+    struct PatchWork { DevBuf rgb, color, depth, jobs, range, out, cv, cv_tmp, items, weights, frange; } patch;      // p2p_xyz_patch_batch (xyz_patch.hip)
     ~Pipeline();
 };
 

@@ -10,6 +10,7 @@
 // reference, with FMA contraction off so thresholds (>0.9, <th, uint8 truncation) see the same
 // values as the numpy formulation.
 #include "pipeline.h"
+#include "resize_rules.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -148,56 +149,10 @@ __host__ __device__ inline bool boxes_ok(const Boxes& b, int H, int W)
 // ------------------------------------------------------------------------------------------
 // skimage-style bilinear sampling helpers
 // ------------------------------------------------------------------------------------------
-struct Tap {
-    int i0, i1;
-    double d;
-};
-
-__device__ inline Tap axis_tap(int o, int n_in, int n_out)
-{
-    // identity resize (every resize of a 128-px crop): src = o * 1.0 + (0.5 - 0.5) = o exactly -- the same taps and weight without the
-    // fp64 division (a quarter of stage2_input_kernel's time at BASELINE.json configs[2])
-    if (n_in == n_out) { Tap t; t.i0 = t.i1 = o; t.d = 0.0; return t; }
-    const double s = (double)n_in / (double)n_out;
-    const double src = (double)o * s + (0.5 * s - 0.5);
-    const double lo = floor(src);
-    Tap t;
-    t.i0 = (int)lo;
-    t.i1 = (int)ceil(src);
-    t.d = src - lo;
-    return t;
-}
-
-__device__ inline int reflect_idx(int i, int n)   // numpy-pad 'reflect' (edge sample not repeated)
-{
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1);
-    i %= p;
-    if (i < 0) i += p;
-    return i >= n ? p - i : i;
-}
-
 // A tap whose weight is exactly zero (d == 0: the source coordinate is an integer, floor == ceil, as in every resize of a
 // 128-px crop) is not evaluated: (1 - 0) * v + 0 * anything-finite == v, so its value can be any finite number.  For the
 // identity resizes of BASELINE.json configs[1-3] that is 1 tap instead of 4 -- and 1 instead of 16 where taps nest.
 #define P2P_TAP_LIVE(a, e, tr, tc) (((a) == 0 || (tr).d != 0) && ((e) == 0 || (tc).d != 0))
-
-__device__ inline double lerp2(double tl, double tr, double bl, double br, double dr, double dc)
-{
-    const double top = (1 - dc) * tl + dc * tr;
-    const double bot = (1 - dc) * bl + dc * br;
-    return (1 - dr) * top + dr * bot;
-}
-
-// skimage's clip=True (every version the reference can run on): the warp output is clamped to [min, max] of the warp
-// INPUT; in 'constant' mode with cval outside that range, outputs exactly equal to cval are left alone
-// (skimage.transform._warps._clip_warp_output).  A no-op unless taps fall outside the image (up-scaling borders) or
-// the anti-aliasing filter mixed cval in.
-__device__ inline double clip_warp(double v, double lo, double hi, double cval)
-{
-    if (!(lo <= cval && cval <= hi) && v == cval) return v;
-    return v < lo ? lo : (v > hi ? hi : v);
-}
 
 // (pixel - 128) / 128 of frame pixel (y, x), channel ch
 __device__ inline double frame_px(const DetInfo& D, int y, int x, int ch)
@@ -655,32 +610,6 @@ __device__ inline void cand_raw(const float* q, double* prob, double* ng, double
 //   taps floorf(c), ceilf(c); dc = c - floorf(c) in float32
 //   top = (1.0 - (double)dc) * (double)tl + (double)(dc * tr)          dc * tr is a float32 product
 //   out = (float)((1.0 - (double)dr) * top + (double)dr * bottom)
-struct TapF {
-    int i0, i1;
-    float d;
-};
-
-__device__ inline TapF axis_tap_f32(int o, int n_in, int n_out)
-{
-    if (n_in == n_out) { TapF t; t.i0 = t.i1 = o; t.d = 0.f; return t; }      // ms = 1, mt = 0: src = (float)o exactly
-    const double s = (double)n_in / (double)n_out;
-    const float ms = (float)s, mt = (float)(s * 0.5 - 0.5);
-    const float src = ms * (float)o + mt;            // contraction is off in this file
-    const float lo = floorf(src);
-    TapF t;
-    t.i0 = (int)lo;
-    t.i1 = (int)ceilf(src);
-    t.d = src - lo;
-    return t;
-}
-
-__device__ inline float lerp2_f32(float tl, float tr, float bl, float br, float dr, float dc)
-{
-    const double top = (1.0 - (double)dc) * (double)tl + (double)(dc * tr);
-    const double bot = (1.0 - (double)dc) * (double)bl + (double)(dc * br);
-    return (float)((1.0 - (double)dr) * top + (double)dr * bot);
-}
-
 // bk: the candidate's five anti-aliased planes [prob | pred r | g | b | non_gray][128*128] (null: raw maps from y2c)
 // gen: 0 = every image warped in double (scikit-image <= 0.14, and 0.15 / 0.16 -- there on the filtered planes `bk`), 1 = 0.17 / 0.18 (prob and
 // img_pred warped in float32, compared with th_inlier and multiplied by 255 in float32; the non_gray image of :146 is a float64 array in every version)

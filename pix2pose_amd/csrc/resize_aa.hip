@@ -57,11 +57,21 @@ double np_sum(const double* a, int n)
 // sigma / radius / one-sided weights for crop side `side` against the 128-px network resolution:
 // side > 128 -> the side x side canvas is filtered before shrinking to 128; side < 128 -> the 128x128 map is filtered
 // before shrinking to side.  Returns the radius (0 = no filtering); w receives radius + 1 values, centre first.
+int aa_weights_for_axis(int n_in_i, int n_out_i, std::vector<double>& w);
+
 int aa_weights_for_side(int side, std::vector<double>& w)
 {
     w.clear();
     if (side <= 0 || side == 128) return 0;
-    const double n_in = side > 128 ? (double)side : 128.0, n_out = side > 128 ? 128.0 : (double)side;
+    return side > 128 ? aa_weights_for_axis(side, 128, w) : aa_weights_for_axis(128, side, w);
+}
+
+// The same for one axis shrinking from n_in to n_out samples (the training patches: each axis has its own factor).
+int aa_weights_for_axis(int n_in_i, int n_out_i, std::vector<double>& w)
+{
+    w.clear();
+    if (n_in_i <= 0 || n_out_i <= 0) return 0;
+    const double n_in = (double)n_in_i, n_out = (double)n_out_i;
     const double factor = n_in / n_out;
     double sigma = (factor - 1) / 2;
     if (!(sigma > 0)) return 0;
@@ -254,6 +264,21 @@ __global__ void aa_range_finish_kernel(AaItem* __restrict__ items, int n_items)
 }
 
 }  // namespace
+
+// An image whose two axes have different Gaussians: rows[i] describes item i's first pass (a -> tmp, the row axis' radius and weights),
+// cols[i] its second (tmp -> a, the column axis').  A pass of radius 0 is skipped, as in launch_aa_filter: the caller points the
+// other pass at the buffer that holds its input.  The range keys are the caller's to take from whichever buffer holds the result.
+hipError_t launch_aa_filter_axes(AaItem* rows, AaItem* cols, int n_items, int max_elems, hipStream_t s)
+{
+    if (n_items <= 0) return hipSuccess;
+    const int bx = std::max(1, std::min(256, (max_elems / AA_V1 + 255) / 256));
+    for (int i0 = 0; i0 < n_items; i0 += 65535) {        // gridDim.y limit
+        const int ni = std::min(65535, n_items - i0);
+        hipLaunchKernelGGL((aa_filter_kernel<0>), dim3(bx, ni), dim3(256), 0, s, rows + i0);
+        hipLaunchKernelGGL((aa_filter_kernel<1>), dim3(bx, ni), dim3(256), 0, s, cols + i0);
+    }
+    return hipGetLastError();
+}
 
 hipError_t launch_aa_filter(AaItem* items, int n_items, int max_elems, hipStream_t s)
 {

@@ -69,7 +69,7 @@ def group_targets(targets):
     return out
 
 
-def _resize_generation(cfg: dict) -> int:
+def resize_generation_of(cfg: dict) -> int:
     """cfg key ``skimage`` ("0.14" | "0.15" | "0.16" | "0.17" | "0.18": the scikit-image the reference environment resolves to -- the
     reference's requirements.txt does not pin it) or the older ``resize_anti_aliasing`` (bool / 0-2).  Neither: generation 0, with a
     warning that it is the one generation no real library in the build image can check."""
@@ -155,7 +155,7 @@ def output_name(dataset):
     return "pix2pose-iccv19_%s-test-primesense.csv" % dataset if dataset == "tless" else "pix2pose-iccv19_%s-test.csv" % dataset
 
 
-def _load_frame(path):
+def load_frame(path):
     if path.endswith(".npy"):
         return np.load(path)
     try:
@@ -183,11 +183,11 @@ class FramePrefetcher:
             return
         for p in paths:
             if p not in self._pending:
-                self._pending[p] = self._pool.submit(_load_frame, p)
+                self._pending[p] = self._pool.submit(load_frame, p)
 
     def get(self, path):
         f = self._pending.pop(path, None)
-        return f.result() if f is not None else _load_frame(path)
+        return f.result() if f is not None else load_frame(path)
 
     def close(self):
         if self._pool is not None:
@@ -363,7 +363,7 @@ def run(cfg: dict, dataset: str, dump: dict, device: int = 0, base_dir: str = ".
             extra = dict(extra, inject1=held[0].data_ptr(), inject2=held[1].data_ptr(), inject_slots=int(held[1].shape[1]))
         try:
             pending = runtime.est_pose_submit(ctx, specs, frames, dets, det_masks=det_masks if det_masks else None,
-                                              anti_aliasing=_resize_generation(cfg),
+                                              anti_aliasing=resize_generation_of(cfg),
                                               **extra)
         except Exception as e:                            # noqa: BLE001
             if gather is None:

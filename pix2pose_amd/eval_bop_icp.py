@@ -30,7 +30,7 @@ import time
 
 import numpy as np
 
-from .eval_bop import (FramePrefetcher, _resize_generation, group_targets, model_params_to_obj_param, outlier_thresholds,
+from .eval_bop import (FramePrefetcher, resize_generation_of, group_targets, model_params_to_obj_param, outlier_thresholds,
                        output_name, rank_image_results, save_bop_results)
 
 
@@ -121,7 +121,7 @@ def run(cfg: dict, dataset: str, dump: dict, device: int = 0, base_dir: str = ".
         gen = runtime.Generator(W.load_weights(wfn, backbone), backbone, ctx)
         specs.append(runtime.ObjectSpec(gen, model_params_to_obj_param(dump["norm_factor"][str(mid)]), th_o[m], th_i))
         meshes.append(runtime.Mesh.from_ply(ctx, os.path.join(base_dir, dump["meshes"][str(mid)])))
-    aa = _resize_generation(cfg)
+    aa = resize_generation_of(cfg)
     rg = runtime.Rgbd(ctx)
     by_image = {(im["scene_id"], im["im_id"]): im for im in dump["images"]}
     tlist = [t + [gi] for gi, t in enumerate(group_targets(dump["targets"]))]

@@ -1,0 +1,111 @@
+"""python -m pix2pose_amd.make_train_xyz <gpu> <cfg.json> <dataset>
+
+The reference's training-data steps 2_1 and 2_2 (tools/2_1_ply_file_to_3d_coord_model.py, tools/2_2_render_pix2pose_training.py)
+on the GPU, for a BOP dataset directory ``<cfg dataset_dir>/<dataset>``:
+
+  * ``models_xyz/`` (XYZ-coloured meshes + ``norm_factor.json``) is written when it is absent;
+  * the training images are listed as tools/bop_io.py lists them: every scene directory of ``train/`` (cfg ``train_dir`` names
+    another split) that has a ``scene_camera.json``, its images in id order; scenes are taken in sorted order (the reference
+    takes them in ``os.listdir`` order, which the file system decides);
+  * per object, the images whose FIRST ground-truth entry is that object are rendered at that pose -- get_sympose applied, the
+    image's own ``cam_K`` except for hb / ycbv / itodd, which use the global camera -- in batches, and each ``[rgb | xyz]`` patch
+    is written to ``train_xyz/<obj:02d>/<n:06d>.npy``, n counting the object's images as the reference's ``xyz_id`` does.
+
+cfg ``skimage`` names the scikit-image generation of the resize of boxes above 128 px, as for eval_bop.  Not written (DESIGN.md
+8.4): the in-plane rotation copies ``<n>_<rot>.npy``, the YCB-V train_real patches.
+"""
+from __future__ import annotations
+
+import json
+import os
+import sys
+
+import numpy as np
+
+from . import runtime
+from .eval_bop import load_frame, resize_generation_of
+from .xyz_model import get_sympose, write_models_xyz
+
+GLOBAL_CAMERA_DATASETS = ("hb", "ycbv", "itodd")
+
+
+def list_training_images(train_dir):
+    """-> list of (rgb path, gts of the image, cam_K [3,3]) in the order described above (scenes without scene_gt.json are left out:
+    the reference's lists would fall out of step on them)."""
+    out = []
+    if not os.path.isdir(train_dir):
+        return out
+    for scene in sorted(os.listdir(train_dir)):
+        d = os.path.join(train_dir, scene)
+        cam_fn, gt_fn = os.path.join(d, "scene_camera.json"), os.path.join(d, "scene_gt.json")
+        if not (os.path.exists(cam_fn) and os.path.exists(gt_fn)):
+            continue
+        cams = {int(k): v for k, v in json.load(open(cam_fn)).items()}
+        gts = {int(k): v for k, v in json.load(open(gt_fn)).items()}
+        for im_id in sorted(cams):
+            out.append((os.path.join(d, "rgb", "%06d.png" % im_id), gts[im_id], np.array(cams[im_id]["cam_K"], np.float64).reshape(3, 3)))
+    return out
+
+
+def run(gpu: int, cfg: dict, dataset: str, batch: int = 32, log=print):
+    """-> {obj_id: number of patches written}"""
+    ddir = os.path.join(cfg["dataset_dir"], dataset)
+    models_dir = os.path.join(ddir, "models")
+    info = json.load(open(os.path.join(models_dir, "models_info.json")))
+    model_ids = sorted(int(k) for k in info if os.path.exists(os.path.join(models_dir, "obj_%06d.ply" % int(k))))
+    xyz_dir = os.path.join(ddir, "models_xyz")
+    if not os.path.exists(xyz_dir):
+        write_models_xyz(models_dir, xyz_dir, model_ids)
+    cam = json.load(open(os.path.join(ddir, "camera_uw.json" if dataset == "ycbv" else "camera.json")))
+    K_global = np.array([[cam["fx"], 0, cam["cx"]], [0, cam["fy"], cam["cy"]], [0, 0, 1]], np.float64)
+    images = list_training_images(os.path.join(ddir, cfg.get("train_dir", "train")))
+    gen = resize_generation_of(cfg)
+    ctx = runtime.Context(int(gpu), max_batch=8)
+    written = {}
+    try:
+        for oid in model_ids:
+            m_info = info[str(oid)]
+            sym = [0.0] * 6
+            if "symmetries_continuous" in m_info:
+                sym[:3] = m_info["symmetries_continuous"][0]["axis"]
+                sym[3:] = m_info["symmetries_continuous"][0]["offset"]
+            mesh = runtime.Mesh.from_xyz_ply(ctx, os.path.join(xyz_dir, "obj_%06d.ply" % oid))
+            out_dir = os.path.join(ddir, "train_xyz", "%02d" % oid)
+            os.makedirs(out_dir, exist_ok=True)
+            mine = [(fn, g[0], K) for fn, g, K in images if g and int(g[0]["obj_id"]) == oid]
+            n_written = 0
+            for b0 in range(0, len(mine), batch):
+                chunk = mine[b0:b0 + batch]
+                frames = [load_frame(fn) for fn, _, _ in chunk]
+                H, W = frames[0].shape[:2]
+                jobs = []
+                for fn, gt, K in chunk:
+                    R, _lock = get_sympose(np.array(gt["cam_R_m2c"], np.float64).reshape(3, 3), sym)
+                    jobs.append({"mesh": 0, "camK": K_global if dataset in GLOBAL_CAMERA_DATASETS else K, "R": R,
+                                 "t": np.array(gt["cam_t_m2c"], np.float64).ravel()})
+                color, depth, bbox = runtime.render_xyz_batch(ctx, [mesh], jobs, H, W)
+                patches = runtime.xyz_patch_batch(ctx, frames, color, depth, bbox, gen)
+                for k, p in enumerate(patches):
+                    if p is None:
+                        log("object %d: %s renders empty, skipped (its number %06d stays unused)" % (oid, chunk[k][0], b0 + k))
+                        continue
+                    np.save(os.path.join(out_dir, "%06d.npy" % (b0 + k)), p)
+                    n_written += 1
+            mesh.close()
+            written[oid] = n_written
+            log("object %d: %d patches" % (oid, n_written))
+    finally:
+        ctx.close()
+    return written
+
+
+def main(argv):
+    if len(argv) < 4:
+        print(__doc__)
+        return 2
+    run(int(argv[1]), json.load(open(argv[2])), argv[3])
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))

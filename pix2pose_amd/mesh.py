@@ -12,6 +12,7 @@ _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short":
               "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
               "double": "f8", "float64": "f8"}
 _FACE_LISTS = ("vertex_indices", "vertex_index")
+_RGB = ("red", "green", "blue")
 
 
 def _parse_header(f):
@@ -51,7 +52,7 @@ def _fan(polys):
     return tris
 
 
-def _read_ascii(f, elements):
+def _read_ascii(f, elements, rgb=None):
     tokens = f.read().split()
     pos = 0
     out = {}
@@ -70,12 +71,15 @@ def _read_ascii(f, elements):
             rows.append(row)
         out[name] = rows
     verts = np.array([[r["x"], r["y"], r["z"]] for r in out.get("vertex", [])], np.float64).reshape(-1, 3)
+    names = {p[0] for e in elements if e[0] == "vertex" for p in e[2]}
+    if rgb is not None and all(c in names for c in _RGB):
+        rgb.append(np.array([[r[c] for c in _RGB] for r in out.get("vertex", [])], np.uint8).reshape(-1, 3))
     key = next((p[0] for e in elements if e[0] == "face" for p in e[2] if p[0] in _FACE_LISTS), None)
     polys = [r[key] for r in out.get("face", [])] if key else []
     return verts, polys
 
 
-def _read_binary(buf, elements):
+def _read_binary(buf, elements, rgb=None):
     pos = 0
     verts, polys = np.zeros((0, 3)), []
     for name, count, props in elements:
@@ -85,6 +89,8 @@ def _read_binary(buf, elements):
             pos += dt.itemsize * count
             if name == "vertex":
                 verts = np.stack([arr["x"], arr["y"], arr["z"]], 1).astype(np.float64)
+                if rgb is not None and all(c in dt.names for c in _RGB):
+                    rgb.append(np.stack([arr[c] for c in _RGB], 1).astype(np.uint8))
             continue
         if len(props) == 1 and count > 0:
             # fast path: every polygon has as many corners as the first (BOP models are all triangles)
@@ -118,15 +124,51 @@ def _read_binary(buf, elements):
     return verts, polys
 
 
-def read_ply(path):
-    """-> (verts float64 [N,3] in the file's units (mm for BOP models), tris int32 [M,3]) with polygons fan-triangulated."""
+def _read(path, rgb):
     with open(path, "rb") as f:
         fmt, elements = _parse_header(f)
         if fmt == "ascii":
-            verts, polys = _read_ascii(f, elements)
+            verts, polys = _read_ascii(f, elements, rgb)
         else:
-            verts, polys = _read_binary(f.read(), elements)
+            verts, polys = _read_binary(f.read(), elements, rgb)
     tris = np.array(_fan(polys), np.int32).reshape(-1, 3)
     if tris.size and (tris.min() < 0 or tris.max() >= len(verts)):
         raise ValueError("%s: a face names a vertex outside [0, %d)" % (path, len(verts)))
     return verts, tris
+
+
+def read_ply(path):
+    """-> (verts float64 [N,3] in the file's units (mm for BOP models), tris int32 [M,3]) with polygons fan-triangulated."""
+    return _read(path, None)
+
+
+def read_ply_rgb(path):
+    """read_ply plus the vertex colours: -> (verts, tris, colors uint8 [N,3] = the vertex element's red, green, blue, or None when
+    it does not have all three)."""
+    rgb = []
+    verts, tris = _read(path, rgb)
+    return verts, tris, (rgb[0] if rgb else None)
+
+
+def write_ply_rgb(path, verts, tris, colors):
+    """A binary_little_endian PLY with float x y z, uchar red green blue and triangle faces (what a models_xyz file needs)."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3)
+    c = np.asarray(colors, np.uint8).reshape(-1, 3)
+    t = np.asarray(tris, np.int32).reshape(-1, 3)
+    if len(c) != len(v):
+        raise ValueError("%d colours for %d vertices" % (len(c), len(v)))
+    va = np.empty(len(v), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]))
+    for k, n in enumerate("xyz"):
+        va[n] = v[:, k]
+    for k, n in enumerate(_RGB):
+        va[n] = c[:, k]
+    fa = np.empty(len(t), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    fa["n"] = 3
+    fa["v"] = t
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %d\n"
+            "property list uchar int vertex_indices\nend_header\n" % (len(v), len(t)))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(va.tobytes())
+        f.write(fa.tobytes())

@@ -451,6 +451,23 @@ class Mesh:
         from .mesh import read_ply
         return cls(ctx, *read_ply(path))
 
+    @classmethod
+    def from_xyz_ply(cls, ctx: Context, path: str) -> "Mesh":
+        """A models_xyz PLY (pix2pose_amd.xyz_model): the mesh with its vertex colours set."""
+        from .xyz_model import read_xyz_model
+        verts, tris, colors = read_xyz_model(path)
+        m = cls(ctx, verts, tris)
+        m.set_colors(colors)
+        return m
+
+    def set_colors(self, colors) -> None:
+        """Per-vertex colours uint8 [N,3] (p2p_mesh_set_colors), what render_xyz_batch interpolates; N must be the vertex count."""
+        c = np.asarray(colors)
+        if c.dtype != np.uint8:
+            raise ValueError("vertex colours must be uint8, got %s" % c.dtype)
+        c = np.ascontiguousarray(c).reshape(-1, 3)
+        _lib.check(_lib.lib().p2p_mesh_set_colors(self._h, c.ctypes.data, len(c)), "p2p_mesh_set_colors")
+
     @property
     def handle(self):
         return self._h
@@ -494,6 +511,47 @@ def render_depth_batch(ctx: Context, meshes, jobs, height: int, width: int):
     _lib.check(_lib.lib().p2p_render_depth_batch(ctx.handle, mh, len(meshes), arr, len(jobs), height, width, out.ctypes.data),
                "p2p_render_depth_batch")
     return out
+
+
+def render_xyz_batch(ctx: Context, meshes, jobs, height: int, width: int):
+    """Colour z-buffer of XYZ-coloured meshes (p2p_render_xyz_batch; replaces get_rendering() of the reference's
+    2_2_render_pix2pose_training.py): -> (color float32 [n, H, W, 3] in [0, 1], channels (x, y, z), 0 where nothing is drawn;
+    depth float32 [n, H, W], bit-identical to render_depth_batch; bbox int32 [n, 4] = [min v, min u, max v, max u] of depth > 0,
+    max inclusive, -1s for an empty render).  jobs as in render_depth_batch; every mesh needs set_colors first."""
+    keep = []
+    arr = _depth_jobs(jobs, keep)
+    mh = (C.c_void_p * max(1, len(meshes)))(*[m.handle.value for m in meshes])
+    color = np.zeros((len(jobs), height, width, 3), np.float32)
+    depth = np.zeros((len(jobs), height, width), np.float32)
+    bbox = np.full((len(jobs), 4), -1, np.int32)
+    _lib.check(_lib.lib().p2p_render_xyz_batch(ctx.handle, mh, len(meshes), arr, len(jobs), height, width, color.ctypes.data,
+                                               depth.ctypes.data, bbox.ctypes.data), "p2p_render_xyz_batch")
+    return color, depth, bbox
+
+
+def xyz_patch_batch(ctx: Context, rgbs, color, depth, bbox, generation: int = 0):
+    """Training patches of colour renders (p2p_xyz_patch_batch; 2_2_render_pix2pose_training.py:168-184): rgbs[k] uint8 [H, W, 3],
+    and color / depth / bbox as render_xyz_batch returned them for the same jobs.  -> a list with, per job, the uint8 [h, w, 6]
+    patch ([rgb | xyz], at most 128 on its longer side) or None for a job that is skipped (empty render, or a box with a zero
+    side).  generation: the scikit-image resize generation of boxes above 128 px (runtime.resize_generation)."""
+    n = len(rgbs)
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    bbox = np.ascontiguousarray(bbox, dtype=np.int32).reshape(-1, 4)
+    if n == 0:
+        return []
+    H, W = depth.shape[1:]
+    if color.shape != (n, H, W, 3) or depth.shape != (n, H, W) or len(bbox) != n:
+        raise ValueError("color / depth / bbox do not describe %d renders of one size" % n)
+    rgbs = [np.ascontiguousarray(r, dtype=np.uint8) for r in rgbs]
+    if any(r.shape != (H, W, 3) for r in rgbs):
+        raise ValueError("every frame must be uint8 [%d, %d, 3]" % (H, W))
+    rp = (C.c_void_p * n)(*[r.ctypes.data for r in rgbs])
+    out = np.zeros((n, 128, 128, 6), np.uint8)
+    shapes = np.zeros((n, 2), np.int32)
+    _lib.check(_lib.lib().p2p_xyz_patch_batch(ctx.handle, rp, color.ctypes.data, depth.ctypes.data, bbox.ctypes.data, n, H, W,
+                                              int(generation), out.ctypes.data, shapes.ctypes.data), "p2p_xyz_patch_batch")
+    return [out[k, :shapes[k, 0], :shapes[k, 1]].copy() if shapes[k, 0] > 0 else None for k in range(n)]
 
 
 def depth_score_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = False):
