@@ -656,6 +656,25 @@ P2P_API int p2p_render_xyz_batch(p2p_ctx* ctx, const p2p_mesh* const* meshes, in
 P2P_API int p2p_xyz_patch_batch(p2p_ctx* ctx, const unsigned char* const* rgb, const float* color, const float* depth, const int* bbox,
                                 int n_jobs, int height, int width, int resize_generation, unsigned char* patches, int* shapes);
 
+/* The in-plane rotation copies of those patches (tools/2_2_render_pix2pose_training.py:64-96, augment_inplane_gen with isYCB=False):
+ * per job a frame and its render as above (uploaded once per job) and n_angles[k] rotations, each given by what
+ * skimage.transform.rotate(resize=True) of scikit-image 0.17 / 0.18 derives from the angle on the host: matrices [item][6] = rows 0 and
+ * 1 of the float64 map (x, y, 1) of the rotated image -> (column, row) of the frame, and rot_shapes [item][2] = the rotated frame's
+ * (rows, columns); items are the jobs' angles in job order (runtime.xyz_rotate_patch_batch forms both with numpy, so their bits do not
+ * depend on the device).  rgb_table / xyz_table: float32 [256], the value the reference's float32 input image holds for the 8-bit
+ * level q -- float32(q / 255.0) for the frame (grey 128 where depth == 0), float32(float32(float32(q) / 255) * 255) / 255 for the
+ * colour's GL level q = floor(c * 255 + 0.5); entries in [0, 1].  Per item: the box of rotate(depth > 0 as float64) > 0 (fp64 warp,
+ * reduced on the device), then per pixel of that box, for both images, the library's float32 warp (cval 0.5 for the frame, 0 for the
+ * colour), its clip to the input image's range, times 255 in float32, truncated to uint8; the crop leaves the box's last row and
+ * column out; boxes above 128 px are resized like p2p_xyz_patch_batch's.  patches: host u8 [items][128][128][6], shapes: host int
+ * [items][2], as above; (0, 0) for an empty render or a box with a zero side.  resize_generation must be 1 (0.17 / 0.18): the other
+ * generations hand a float32 image to the warp differently and no real library pins them.  A bad angle list (a negative count, a
+ * matrix that is not finite, an impossible shape) is P2P_ERR_INVALID_ARG.  An item's result is bit-identical alone or in a batch. */
+P2P_API int p2p_xyz_rotate_patch_batch(p2p_ctx* ctx, const unsigned char* const* rgb, const float* color, const float* depth, int n_jobs,
+                                       int height, int width, const int* n_angles, const double* matrices, const int* rot_shapes,
+                                       const float* rgb_table, const float* xyz_table, int resize_generation, unsigned char* patches,
+                                       int* shapes);
+
 #ifdef __cplusplus
 }
 #endif

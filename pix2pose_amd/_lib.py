@@ -305,6 +305,7 @@ def lib():
     L.p2p_mesh_set_colors.argtypes = [vp, vp, ci]
     L.p2p_render_xyz_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci, vp, vp, vp]
     L.p2p_xyz_patch_batch.argtypes = [vp, C.POINTER(vp), vp, vp, vp, ci, ci, ci, ci, vp, vp]
+    L.p2p_xyz_rotate_patch_batch.argtypes = [vp, C.POINTER(vp), vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp]
     _lib = L
     return L
 

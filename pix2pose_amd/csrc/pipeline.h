@@ -215,6 +215,7 @@ struct Pipeline {
     // grow-only workspaces of p2p_render_xyz_batch (depth.hip): winner keys, colour and depth images, boxes, job records
     struct XyzWork { DevBuf key, color, depth, bbox, jobs; } xyz;
     struct PatchWork { DevBuf rgb, color, depth, jobs, range, out, cv, cv_tmp, items, weights, frange; } patch;      // p2p_xyz_patch_batch (xyz_patch.hip)
+    struct RotWork { DevBuf lv, tabs, rng, items, box, crop; } rot;      // p2p_xyz_rotate_patch_batch (xyz_patch.hip); frames and slots live in patch
     ~Pipeline();
 };
 

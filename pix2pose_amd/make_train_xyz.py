@@ -11,8 +11,13 @@ on the GPU, for a BOP dataset directory ``<cfg dataset_dir>/<dataset>``:
     image's own ``cam_K`` except for hb / ycbv / itodd, which use the global camera -- in batches, and each ``[rgb | xyz]`` patch
     is written to ``train_xyz/<obj:02d>/<n:06d>.npy``, n counting the object's images as the reference's ``xyz_id`` does.
 
-cfg ``skimage`` names the scikit-image generation of the resize of boxes above 128 px, as for eval_bop.  Not written (DESIGN.md
-8.4): the in-plane rotation copies ``<n>_<rot>.npy``, the YCB-V train_real patches.
+cfg ``skimage`` names the scikit-image generation of the resize of boxes above 128 px, as for eval_bop.
+
+cfg ``augment_inplane`` (degrees, default 0 = none; the reference's script has 30 written into it) adds the in-plane rotation copies
+of augment_inplane_gen (2_2:64-96): next to each ``<n:06d>.npy`` the files ``<n:06d>_<rot:03d>.npy`` for rot in
+np.arange(step, 360, step), unless get_sympose locks the rotation (a symmetry axis along the camera axis).  They are rotated by the
+rules of scikit-image 0.17 / 0.18, the one generation pinned to a real library, so a value above 0 with any other ``skimage`` raises
+ValueError before a file is written.  Not written: the YCB-V train_real patches and their mask channel.
 """
 from __future__ import annotations
 
@@ -27,6 +32,22 @@ from .eval_bop import load_frame, resize_generation_of
 from .xyz_model import get_sympose, write_models_xyz
 
 GLOBAL_CAMERA_DATASETS = ("hb", "ycbv", "itodd")
+ROTATE_GENERATION = 1      # runtime.RESIZE_GENERATIONS: scikit-image 0.17 / 0.18
+
+
+def inplane_angles(cfg: dict, gen: int):
+    """-> the rotations (degrees, ints) of cfg ``augment_inplane``; [] for the default 0.  ValueError for a step that is not a
+    positive whole number of degrees below 360 or a resize generation whose rotate is not built."""
+    step = cfg.get("augment_inplane", 0)
+    if isinstance(step, bool) or not isinstance(step, (int, float)) or step != int(step) or not 0 <= step < 360:
+        raise ValueError("augment_inplane must be a whole number of degrees in [0, 360), got %r" % (step,))
+    if step == 0:
+        return []
+    if gen != ROTATE_GENERATION:
+        raise ValueError("augment_inplane=%d needs skimage '0.17' or '0.18': the in-plane rotation copies are built for that generation "
+                         "of skimage.transform.rotate only (the one pinned to a real library), the cfg names generation %d"
+                         % (int(step), gen))
+    return [int(r) for r in np.arange(int(step), 360, int(step))]
 
 
 def list_training_images(train_dir):
@@ -48,7 +69,9 @@ def list_training_images(train_dir):
 
 
 def run(gpu: int, cfg: dict, dataset: str, batch: int = 32, log=print):
-    """-> {obj_id: number of patches written}"""
+    """-> {obj_id: number of patches <n>.npy written} (the rotation copies are not counted)"""
+    gen = resize_generation_of(cfg)
+    angles = inplane_angles(cfg, gen)          # raises before anything is written
     ddir = os.path.join(cfg["dataset_dir"], dataset)
     models_dir = os.path.join(ddir, "models")
     info = json.load(open(os.path.join(models_dir, "models_info.json")))
@@ -59,7 +82,6 @@ def run(gpu: int, cfg: dict, dataset: str, batch: int = 32, log=print):
     cam = json.load(open(os.path.join(ddir, "camera_uw.json" if dataset == "ycbv" else "camera.json")))
     K_global = np.array([[cam["fx"], 0, cam["cx"]], [0, cam["fy"], cam["cy"]], [0, 0, 1]], np.float64)
     images = list_training_images(os.path.join(ddir, cfg.get("train_dir", "train")))
-    gen = resize_generation_of(cfg)
     ctx = runtime.Context(int(gpu), max_batch=8)
     written = {}
     try:
@@ -78,19 +100,27 @@ def run(gpu: int, cfg: dict, dataset: str, batch: int = 32, log=print):
                 chunk = mine[b0:b0 + batch]
                 frames = [load_frame(fn) for fn, _, _ in chunk]
                 H, W = frames[0].shape[:2]
-                jobs = []
+                jobs, locks = [], []
                 for fn, gt, K in chunk:
-                    R, _lock = get_sympose(np.array(gt["cam_R_m2c"], np.float64).reshape(3, 3), sym)
+                    R, lock = get_sympose(np.array(gt["cam_R_m2c"], np.float64).reshape(3, 3), sym)
                     jobs.append({"mesh": 0, "camK": K_global if dataset in GLOBAL_CAMERA_DATASETS else K, "R": R,
                                  "t": np.array(gt["cam_t_m2c"], np.float64).ravel()})
+                    locks.append(lock)
                 color, depth, bbox = runtime.render_xyz_batch(ctx, [mesh], jobs, H, W)
                 patches = runtime.xyz_patch_batch(ctx, frames, color, depth, bbox, gen)
+                copies = None
+                if angles:
+                    copies = runtime.xyz_rotate_patch_batch(ctx, frames, color, depth, [[] if lock else angles for lock in locks], gen)
                 for k, p in enumerate(patches):
                     if p is None:
                         log("object %d: %s renders empty, skipped (its number %06d stays unused)" % (oid, chunk[k][0], b0 + k))
                         continue
                     np.save(os.path.join(out_dir, "%06d.npy" % (b0 + k)), p)
                     n_written += 1
+                    if copies and not locks[k]:
+                        for rot, q in zip(angles, copies[k]):
+                            if q is not None:
+                                np.save(os.path.join(out_dir, "%06d_%03d.npy" % (b0 + k, rot)), q)
             mesh.close()
             written[oid] = n_written
             log("object %d: %d patches" % (oid, n_written))

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -552,6 +553,136 @@ def xyz_patch_batch(ctx: Context, rgbs, color, depth, bbox, generation: int = 0)
     _lib.check(_lib.lib().p2p_xyz_patch_batch(ctx.handle, rp, color.ctypes.data, depth.ctypes.data, bbox.ctypes.data, n, H, W,
                                               int(generation), out.ctypes.data, shapes.ctypes.data), "p2p_xyz_patch_batch")
     return [out[k, :shapes[k, 0], :shapes[k, 1]].copy() if shapes[k, 0] > 0 else None for k in range(n)]
+
+
+def _rot_mm(a, b):
+    """a @ b in plain double products summed in index order, no fused multiply-add: what numpy's matmul gave under the library for
+    these 3-column operands, written out so that the bits do not depend on the BLAS underneath."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    out = np.zeros((a.shape[0], b.shape[1]))
+    for i in range(a.shape[0]):
+        for j in range(b.shape[1]):
+            s = float(a[i, 0]) * float(b[0, j])
+            for k in range(1, a.shape[1]):
+                s = s + float(a[i, k]) * float(b[k, j])
+            out[i, j] = s
+    return out
+
+
+def _rot_inv3(m):
+    """np.linalg.inv of a 3 x 3 matrix as LAPACK's dgesv computes it (held bit for bit to numpy 1.26 / OpenBLAS on the matrices of
+    rotate): LU with partial pivoting, the column below a pivot scaled by the pivot's reciprocal, plain multiply-subtract updates,
+    then per column of the identity the forward substitution and a back substitution that multiplies by the diagonal's reciprocal."""
+    n = 3
+    A = [[float(m[i][j]) for j in range(n)] for i in range(n)]
+    B = [[1.0 if i == j else 0.0 for j in range(n)] for i in range(n)]
+    for k in range(n):
+        p = max(range(k, n), key=lambda i: (abs(A[i][k]), -i))
+        if p != k:
+            A[k], A[p] = A[p], A[k]
+            B[k], B[p] = B[p], B[k]
+        r = 1.0 / A[k][k]
+        for i in range(k + 1, n):
+            A[i][k] = A[i][k] * r
+        for i in range(k + 1, n):
+            for j in range(k + 1, n):
+                A[i][j] = A[i][j] - A[i][k] * A[k][j]
+    for c in range(n):
+        for k in range(n):
+            for i in range(k + 1, n):
+                B[i][c] = B[i][c] - A[i][k] * B[k][c]
+        for k in range(n - 1, -1, -1):
+            B[k][c] = B[k][c] * (1.0 / A[k][k])
+            for i in range(k):
+                B[i][c] = B[i][c] - A[i][k] * B[k][c]
+    return np.array(B)
+
+
+def skimage_rotate_matrix(rows: int, cols: int, angle: float):
+    """What skimage.transform.rotate(image [rows, cols], angle, resize=True) of scikit-image 0.17 / 0.18 hands to its warp, with the
+    library's operations in the library's order (its matmul and linalg.inv written out in plain double arithmetic, _rot_mm and
+    _rot_inv3, so that the bits do not depend on the BLAS / LAPACK build under numpy): -> (float64 [3, 3] map from (x, y, 1) of the rotated image to (column, row,
+    1) of the input, (out_rows, out_cols)).  tform3 + tform2 + tform1 is t1 @ (t2 @ t3) in that association (a + b multiplies
+    b.params @ a.params), the shape comes from the inverse image of the four corners, and the translation to the corner minimum is
+    multiplied on the right."""
+    def translation(tx, ty):
+        m = np.array([[1.0, -0.0, 0], [0.0, 1.0, 0], [0, 0, 1]])
+        m[0:2, 2] = (tx, ty)
+        return m
+    a = np.deg2rad(angle)
+    center = np.array((cols, rows)) / 2. - 0.5
+    t2 = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]])
+    m = _rot_mm(translation(*center), _rot_mm(t2, translation(*(-center))))
+    corners = np.array([[0, 0], [0, rows - 1], [cols - 1, rows - 1], [cols - 1, 0]])
+    x, y = np.transpose(corners)
+    dst = _rot_mm(np.vstack((x, y, np.ones_like(x))).T, _rot_inv3(m).T)
+    dst[dst[:, 2] == 0, 2] = np.finfo(float).eps
+    dst[:, :2] /= dst[:, 2:3]
+    minc, minr, maxc, maxr = dst[:, 0].min(), dst[:, 1].min(), dst[:, 0].max(), dst[:, 1].max()
+    shape = np.around((maxr - minr + 1, maxc - minc + 1)).astype(int)
+    m = _rot_mm(m, translation(minc, minr))
+    m[2] = (0, 0, 1)
+    return m, (int(shape[0]), int(shape[1]))
+
+
+def rotate_input_tables():
+    """The float32 value of the two images the reference's augment_inplane_gen rotates, per 8-bit level q: (rgb, xyz), float32 [256]
+    each.  rgb: (img / 255).astype(float32) of the uint8 frame.  xyz: the render is read back as float32(q) / 255, multiplied by 255 in
+    float32 (get_rendering), and (img_r / 255) divides that float32 array again."""
+    q = np.arange(256)
+    rgb = (q.astype(np.uint8) / 255).astype(np.float32)
+    qf = q.astype(np.float32)
+    xyz = ((qf / np.float32(255)) * np.float32(255)) / np.float32(255)
+    return np.ascontiguousarray(rgb), np.ascontiguousarray(xyz, dtype=np.float32)
+
+
+def xyz_rotate_patch_batch(ctx: Context, rgbs, color, depth, angles, generation: int = 1):
+    """The in-plane rotation copies of the training patches (p2p_xyz_rotate_patch_batch; 2_2_render_pix2pose_training.py:64-96):
+    rgbs / color / depth as for xyz_patch_batch, angles[k] the rotations of job k in degrees (lists of different lengths are fine,
+    an empty one too).  -> per job a list with, per angle, the uint8 [h, w, 6] patch or None (empty render, zero-sided box).
+    generation must be 1 (scikit-image 0.17 / 0.18).  Frame and render travel to the device once per job."""
+    n = len(rgbs)
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if n == 0:
+        return []
+    if depth.ndim != 3:
+        raise ValueError("depth must be float32 [n, H, W]")
+    H, W = depth.shape[1:]
+    if color.shape != (n, H, W, 3) or depth.shape != (n, H, W) or len(angles) != n:
+        raise ValueError("color / depth / angles do not describe %d renders of one size" % n)
+    rgbs = [np.ascontiguousarray(r, dtype=np.uint8) for r in rgbs]
+    if any(r.shape != (H, W, 3) for r in rgbs):
+        raise ValueError("every frame must be uint8 [%d, %d, 3]" % (H, W))
+    counts = np.array([len(a) for a in angles], np.int32)
+    total = int(counts.sum())
+    mats = np.zeros((max(1, total), 6), np.float64)
+    rshapes = np.zeros((max(1, total), 2), np.int32)
+    cache = {}
+    i = 0
+    for a_list in angles:
+        for a in a_list:
+            a = float(a)
+            if a not in cache:
+                if np.isfinite(a):
+                    m, s = skimage_rotate_matrix(H, W, a)
+                    cache[a] = (m[:2].ravel(), s)
+                else:
+                    cache[a] = (np.full(6, np.nan), (0, 0))        # the library call names the bad angle list
+            mats[i], rshapes[i] = cache[a]
+            i += 1
+    rgb_tab, xyz_tab = rotate_input_tables()
+    rp = (C.c_void_p * n)(*[r.ctypes.data for r in rgbs])
+    out = np.zeros((max(1, total), 128, 128, 6), np.uint8)
+    shapes = np.zeros((max(1, total), 2), np.int32)
+    _lib.check(_lib.lib().p2p_xyz_rotate_patch_batch(ctx.handle, rp, color.ctypes.data, depth.ctypes.data, n, H, W, counts.ctypes.data,
+                                                     mats.ctypes.data, rshapes.ctypes.data, rgb_tab.ctypes.data, xyz_tab.ctypes.data,
+                                                     int(generation), out.ctypes.data, shapes.ctypes.data), "p2p_xyz_rotate_patch_batch")
+    res, i = [], 0
+    for a_list in angles:
+        res.append([out[i + j, :shapes[i + j, 0], :shapes[i + j, 1]].copy() if shapes[i + j, 0] > 0 else None for j in range(len(a_list))])
+        i += len(a_list)
+    return res
 
 
 def depth_score_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = False):

@@ -122,8 +122,7 @@ def get_sympose(R, sym):
     decomposed in that order, the angles about the flagged axes are zeroed and the matrix is recomposed -- so R = R' @ (a
     rotation about the symmetry axis), and every pose of a symmetric object that looks the same renders the same target.
     rotation_lock is True when the recomposed pose carries the symmetry axis within |axis . z| > 0.8 of the camera axis: the
-    reference then skips its in-plane rotation copies.  Nothing in this package consumes the flag yet (those copies are not
-    built); it is returned so that a caller that adds them can.  Without a symmetry R is returned unchanged."""
+    reference then skips its in-plane rotation copies, and so does make_train_xyz.  Without a symmetry R is returned unchanged."""
     R = np.asarray(R, np.float64).reshape(3, 3)
     sym = np.asarray(sym, np.float64).ravel()
     if not np.sum(sym) > 0:
