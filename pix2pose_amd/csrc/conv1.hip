@@ -12,14 +12,10 @@
 //
 // GEMM orientation: rows = 16 output channels, columns = 16 consecutive output pixels, so a lane ends
 // up with 4 consecutive channels of one pixel (float4 store).
-#include "kernels.h"
+#include "device_common.h"
 #include <cstdlib>
 
 namespace p2p {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -89,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void conv1_f16x3_kernel(const float* __rest
             const int r = idx >> 7, px = idx & 127;
             const int iy = iy0 + r;
             const bool ok = r < C1_ROWS_IN && iy >= 0 && iy < C1_HIN;
-            const unsigned off = ok ? (unsigned)((((size_t)n * C1_HIN + iy) * C1_HIN + px) * 12) : 0xFFFFFFF0u;
+            const unsigned off = ok ? (unsigned)((((size_t)n * C1_HIN + iy) * C1_HIN + px) * 12) : OOB;
             // three dword loads: hipcc (ROCm 7.2) lowers __builtin_amdgcn_raw_buffer_load_b96 to ONE dword
 #pragma unroll
             for (int e = 0; e < 3; ++e) rx[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_x, off, e * 4, 0));
@@ -101,14 +97,11 @@ __global__ __launch_bounds__(256, 2) void conv1_f16x3_kernel(const float* __rest
             const int idx = tid + 256 * j;
             const int r = idx >> 7, px = idx & 127;
             if (r >= C1_ROWS_IN) continue;
-            const float* v = rx[j];
-            const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h2 = __builtin_amdgcn_cvt_pkrtz(v[2], 0.f);
-            fp16x2 l01, l2;
-            l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-            l2[0] = (__fp16)(v[2] - (float)h2[0]); l2[1] = (__fp16)0.f;
+            uint2 hi, lo;
+            split3(rx[j], hi, lo);
             char* d = xs + r * C1_ROW_BYTES + (px + C1_PAD) * 8;
-            *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h2));
-            *reinterpret_cast<uint2*>(d + C1_PLANE) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l2));
+            *reinterpret_cast<uint2*>(d) = hi;
+            *reinterpret_cast<uint2*>(d + C1_PLANE) = lo;
         }
     };
 
@@ -188,12 +181,7 @@ __global__ __launch_bounds__(256, 2) void conv1_f16x3_kernel(const float* __rest
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float u = fmaf(acc[m][q][e], sc[e], sh[e]);
-                        if (act == ACT_RELU) u = relu_nan(u);
-                        else if (act == ACT_LEAKY) u = u > 0.f ? u : u * alpha;
-                        v[m][q][e] = u;
-                    }
+                    for (int e = 0; e < 4; ++e) v[m][q][e] = bn_act1(acc[m][q][e], sc[e], sh[e], act, alpha);
 #pragma unroll
                 for (int m = 0; m < 2; ++m) amax = range_note4(amax, v[m][q]);      // the pooled values are maxima of these
             }
@@ -227,14 +215,9 @@ __global__ __launch_bounds__(256, 2) void conv1_f16x3_kernel(const float* __rest
             for (int q = 0; q < 4; ++q) {
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + q * 16 + lg * 4);
                 const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + q * 16 + lg * 4);
-                f32x4 v = acc[m][q];
+                f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float u = fmaf(v[e], sc[e], sh[e]);
-                    if (act == ACT_RELU) u = relu_nan(u);
-                    else if (act == ACT_LEAKY) u = u > 0.f ? u : u * alpha;
-                    v[e] = u;
-                }
+                for (int e = 0; e < 4; ++e) v[e] = bn_act1(acc[m][q][e], sc[e], sh[e], act, alpha);
                 amax = range_note4(amax, v);
                 *reinterpret_cast<f32x4*>(op + q * 16) = v;
             }

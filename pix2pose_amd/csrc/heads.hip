@@ -13,14 +13,10 @@
 // the GEMM is taken transposed (rows = the 16 outputs, columns = 16 consecutive pixels) so that a lane
 // ends up with (x, y, z, prob) of one output pixel and stores a float4.  PREC_F32 models keep the
 // generic kernel.
-#include "kernels.h"
+#include "device_common.h"
 #include <cstdlib>
 
 namespace p2p {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -78,8 +74,7 @@ __global__ __launch_bounds__(256, 2) void heads_halo_kernel(const IgemmParams p)
     const float* shift = p.shift;
     if (p.n_groups > 1) {
         const int row = n * p.Hg * p.Wg;
-        int g = 0;
-        while (g + 1 < p.n_groups && p.grp[g + 1].row0 <= row) ++g;
+        const int g = group_of<&IgemmGroup::row0>(p.grp, p.n_groups, row);
         w = p.grp[g].w; scale = p.grp[g].scale; shift = p.grp[g].shift;
     }
 
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void heads_halo_kernel(const IgemmParams p)
             const int r = pix >> 6, x = pix & 63;
             const int gy = row0 + r;
             const unsigned off = (r < nrows && gy >= 0 && gy < p.Hg)
-                ? (unsigned)(((((long long)n * p.Hg + gy) * HEADS_W + x) * HEADS_CIN + lq * 4) * 4) : 0xFFFFFFF0u;
+                ? (unsigned)(((((long long)n * p.Hg + gy) * HEADS_W + x) * HEADS_CIN + lq * 4) * 4) : OOB;
             rx[set][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_x, off, chunk * 128, 0));
         }
     };
@@ -119,13 +114,10 @@ __global__ __launch_bounds__(256, 2) void heads_halo_kernel(const IgemmParams p)
             if (r >= nrows) continue;
             const int ring = (row0 + r + HEADS_RING) % HEADS_RING;          // row -1 -> slot 5
             char* dst = smem + l_dst + (ring * HEADS_WP + x + 1) * 16;
-            const f32x4 v = rx[set][j];
-            const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-            fp16x2 l01, l23;
-            l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-            l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
-            *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-            *reinterpret_cast<uint2*>(dst + HEADS_LO) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+            uint2 hi, lo;
+            split4(rx[set][j], hi, lo);
+            *reinterpret_cast<uint2*>(dst) = hi;
+            *reinterpret_cast<uint2*>(dst + HEADS_LO) = lo;
         }
     };
 
@@ -264,9 +256,8 @@ __global__ __launch_bounds__(256, 2) void heads_halo_kernel(const IgemmParams p)
         for (int o = 0; o < HEADS_TH; ++o) {
             const int oy = 2 * (gy_first + step * HEADS_TH + o) + (lg >> 1);
             const int ox = 2 * (16 * wave + li) + (lg & 1);
-            f32x4 v = acc[step][o], q;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
+            const f32x4 v = bn4(acc[step][o], sc, sh);
+            f32x4 q;
             q[0] = tanhf(v[0]); q[1] = tanhf(v[1]); q[2] = tanhf(v[2]);
             q[3] = 1.f / (1.f + __expf(-v[3]));
             *reinterpret_cast<f32x4*>(p.out + (((size_t)n * p.Hout + oy) * p.Wout + ox) * 4) = q;

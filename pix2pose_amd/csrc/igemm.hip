@@ -33,14 +33,9 @@
 //              pre-scaled by 2^10 so their lo parts stay in the f16 normal range (the epilogue scale
 //              carries 2^-10).  Error vs exact fp32 products ~2^-22 relative: the network output moves
 //              by ~1e-6, the same size as fp32 summation-order noise (tests hold both modes to 1e-4).
-#include "kernels.h"
+#include "device_common.h"
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int LDS_LD = IGEMM_BK + 4;  // padded row stride (floats)
 
@@ -76,14 +71,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
     // ---- XCD-aware tile mapping: workgroup b runs on XCD b%8; give each XCD a contiguous
     //      run of tiles (n-tile fastest) so A rows and the weight panel are shared in its L2.
     const int tiles_n = (p.Cout + BN - 1) / BN;
-    const int nblk = gridDim.x;
-    int t;
-    {
-        const int b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int t = xcd_first_tile(gridDim.x, blockIdx.x);
     const int tile_n = t % tiles_n;
     const int tile_m = t / tiles_n;
     const int n0 = tile_n * BN;
@@ -93,8 +81,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
     const float* gscale = p.scale;
     const float* gshift = p.shift;
     if (p.n_groups > 1) {
-        int g = 0;
-        while (g + 1 < p.n_groups && tile_m >= p.grp[g + 1].tile0) ++g;
+        const int g = group_of<&IgemmGroup::tile0>(p.grp, p.n_groups, tile_m);
         m0 = p.grp[g].row0 + (tile_m - p.grp[g].tile0) * BM;
         m_end = p.grp[g + 1].row0;
         gw = p.grp[g].w; gscale = p.grp[g].scale; gshift = p.grp[g].shift;
@@ -138,7 +125,6 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
     //      image is a per-row bit mask computed once per tile.
     const int lrow = tid >> 3;
     const int lcol = (tid & 7) * 4;
-    constexpr unsigned OOB = 0xFFFFFFF0u;
     unsigned a_off0[A_PASSES], a_off1[A_PASSES], a_mask[A_PASSES];
 #pragma unroll
     for (int j = 0; j < A_PASSES; ++j) {
@@ -202,14 +188,11 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
             // row image [hi f16 x32 | lo f16 x32] (128 B): this thread owns k = lcol .. lcol+3
 #pragma unroll
             for (int j = 0; j < A_PASSES; ++j) {
-                const f32x4 v = ra[j];
-                const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-                fp16x2 l01, l23;          // residuals are exact in fp32; round them to nearest
-                l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-                l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
+                uint2 hi, lo;
+                split4(ra[j], hi, lo);
                 char* row = reinterpret_cast<char*>(As + (lrow + 32 * j) * LDS_LD);
-                *reinterpret_cast<uint2*>(row + lcol * 2) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-                *reinterpret_cast<uint2*>(row + 64 + lcol * 2) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+                *reinterpret_cast<uint2*>(row + lcol * 2) = hi;
+                *reinterpret_cast<uint2*>(row + 64 + lcol * 2) = lo;
             }
         } else {
 #pragma unroll
@@ -356,9 +339,7 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
                 for (int it = 0; it < NIT; ++it) {
                     const int op = ops[it];
                     if (op < 0) continue;
-                    f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
+                    f32x4 v = bn4(*reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4), sc, sh);
                     if (p.mode == EPI_HEAD) {
                         // col = phase*4 + ch: this thread holds (x, y, z, prob) of output pixel (2gy+py, 2gx+px)
                         const int ph = col >> 2;
@@ -367,6 +348,8 @@ __global__ __launch_bounds__(256, 3) void igemm_kernel(const IgemmParams p)   //
                         o[3] = 1.f / (1.f + __expf(-v[3]));
                         *reinterpret_cast<f32x4*>(p.out + (size_t)(op + (ph >> 1) * p.Wout + (ph & 1)) * 4) = o;
                     } else {
+                        // bn_act4's residual form (device_common.h) written out: its fmaf is shared with the head branch above, and as a call
+                        // the kernel's register allocation moved
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] += rs[it][e];
                         if (p.act == ACT_RELU) {
@@ -427,9 +410,7 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, int kspl
         float s = 0.f;
         for (int z = 0; z < ksplit; ++z) s += partial[(size_t)z * total + i];
         const int c = (int)(i % Cout);
-        float v = fmaf(s, scale ? scale[c] : 1.f, shift ? shift[c] : 0.f);
-        if (act == ACT_RELU) v = relu_nan(v);
-        else if (act == ACT_LEAKY) v = v > 0.f ? v : v * alpha;
+        const float v = bn_act1(s, scale ? scale[c] : 1.f, shift ? shift[c] : 0.f, act, alpha);
         amax = range_note1(amax, v);
         out[i] = v;
     }
@@ -453,7 +434,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_groups_kernel(const float* 
                                                                     int act, float alpha, float* __restrict__ out, unsigned* __restrict__ range_acc)
 {
     const int m = blockIdx.x;
-    int g = 0;
+    int g = 0;      // (Conv1Groups keeps its runs in a plain array: no group_of)
     while (g + 1 < G.n_groups && G.start[g + 1] <= m) ++g;
     const float* __restrict__ scale = G.scale[g];
     const float* __restrict__ shift = G.shift[g];
@@ -463,9 +444,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_groups_kernel(const float* 
         const size_t o = (size_t)m * Cout + c;
         float s = 0.f;
         for (int z = 0; z < ksplit; ++z) s += partial[(size_t)z * slab + o];
-        float v = fmaf(s, scale ? scale[c] : 1.f, shift ? shift[c] : 0.f);
-        if (act == ACT_RELU) v = relu_nan(v);
-        else if (act == ACT_LEAKY) v = v > 0.f ? v : v * alpha;
+        const float v = bn_act1(s, scale ? scale[c] : 1.f, shift ? shift[c] : 0.f, act, alpha);
         amax = range_note1(amax, v);
         out[o] = v;
     }

@@ -12,15 +12,10 @@
 // Serves Conv2D 3x3 / 5x5 stride 1 'SAME', the transposed-conv phases (2x2 .. 3x3 taps, os = 2) and the
 // two-segment skip concatenations (reference ae_model.py:193-231, resnet50_mod.py:40-118) whenever the
 // grid is a multiple of the 8x16 patch; everything else stays on igemm.hip.
-#include "kernels.h"
+#include "igemm_halo_common.h"
 #include <algorithm>
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -73,13 +68,7 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
     // XCD-aware tile order (block b runs on XCD b % 8): contiguous runs of tiles per XCD, n-tile fastest
     const int tiles_n = (p.Cout + BN - 1) / BN;
     const int tiles_x = p.Wg / TX, tiles_y = p.Hg / TY;
-    int t;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    int t = xcd_first_tile(gridDim.x, blockIdx.x);
     const int tile_n = t % tiles_n;
     int tm = t / tiles_n;
     const int tx0 = (tm % tiles_x) * TX; tm /= tiles_x;
@@ -92,8 +81,7 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
     const float* gshift = p.shift;
     if (p.n_groups > 1) {                       // groups are runs of samples
         const int row = n * p.Hg * p.Wg;
-        int g = 0;
-        while (g + 1 < p.n_groups && p.grp[g + 1].row0 <= row) ++g;
+        const int g = group_of<&IgemmGroup::row0>(p.grp, p.n_groups, row);
         gw = p.grp[g].w; gscale = p.grp[g].scale; gshift = p.grp[g].shift;
     }
 
@@ -102,11 +90,9 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
     // ---- halo loader: float4 idx = tid + 256 j -> quad idx % 8 of halo pixel perm(idx / 8).  The ds_write_b64 stores are
     //      served in contiguous 16-lane groups over 32 banks: two pixels per group, which collide unless they are 4 records
     //      apart (4 * 36 dwords = 16 mod 32) -- so consecutive octets of lanes take pixels hp and hp + 4.
-    constexpr unsigned OOB = 0xFFFFFFF0u;
     unsigned h_pix[HALO_PASSES];               // pixel index into the input tensor, OOB outside the image / the halo
-    unsigned h_dst2[(HALO_PASSES + 1) / 2];    // LDS byte offsets, two 16-bit values per register (0xFFFF = not part of the halo)
-#pragma unroll
-    for (int j = 0; j < (HALO_PASSES + 1) / 2; ++j) h_dst2[j] = 0xFFFFFFFFu;
+    HaloDst<HALO_PASSES> h_dst;                // LDS byte offsets of the passes
+    h_dst.clear();
 #pragma unroll
     for (int j = 0; j < HALO_PASSES; ++j) {
         const int idx = tid + 256 * j;
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
         const bool ok = hp < halo_px && (unsigned)iy < (unsigned)p.Hin && (unsigned)ix < (unsigned)p.Win;
         h_pix[j] = ok ? (unsigned)((n * p.Hin + iy) * p.Win + ix) : OOB;
         const unsigned dst = hp < halo_px ? (unsigned)(hy * PITCH + hx * REC + q * 8) : 0xFFFFu;
-        h_dst2[j >> 1] = (j & 1) ? ((h_dst2[j >> 1] & 0x0000FFFFu) | (dst << 16)) : ((h_dst2[j >> 1] & 0xFFFF0000u) | dst);
+        h_dst.set(j, dst);
     }
     const int hq4 = (tid & 7) * 4;             // channel offset of this thread's quad inside the slice
     const __amdgpu_buffer_rsrc_t rs_a0 = __builtin_amdgcn_make_buffer_rsrc((void*)p.seg[0].ptr, 0, p.seg_bytes[0], 0x00020000);
@@ -136,20 +122,7 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
                                                  : __builtin_amdgcn_raw_buffer_load_b128(rs_a0, off, 0, 0));
         }
     };
-    auto hstore = [&]() {
-#pragma unroll
-        for (int j = 0; j < HALO_PASSES; ++j) {
-            const unsigned dst = (j & 1) ? (h_dst2[j >> 1] >> 16) : (h_dst2[j >> 1] & 0xFFFFu);
-            if (dst == 0xFFFFu) continue;
-            const f32x4 v = rh[j];
-            const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-            fp16x2 l01, l23;          // residuals are exact in fp32; round them to nearest
-            l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-            l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
-            *reinterpret_cast<uint2*>(smem + dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-            *reinterpret_cast<uint2*>(smem + dst + 64) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-        }
-    };
+    auto hstore = [&]() { halo_store(smem, h_dst, rh); };
 
     // ---- weight loader: rows (tid >> 3) + 32 j of the n-tile, 16-byte segment (tid & 7)
     const int lrow = tid >> 3;
@@ -295,16 +268,7 @@ __global__ __launch_bounds__(256, WGM == 2 ? 3 : 2) void igemm_halo_kernel(const
             }
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-                f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]) + rs[it][e];
-                if (p.act == ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
-                } else if (p.act == ACT_LEAKY) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
-                }
+                const f32x4 v = bn_act4(*reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4), sc, sh, rs[it], p.act, p.alpha);
                 amax = range_note4(amax, v);
                 *reinterpret_cast<f32x4*>(p.out + (size_t)ops[it] * p.out_cstride + p.out_coff + col) = v;
             }

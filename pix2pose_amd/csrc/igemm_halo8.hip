@@ -18,15 +18,10 @@
 // LDS banking: an MFMA fragment of 32 rows is 4 grid rows x 8 columns; ds_read_b128 serves 16-lane groups that hold
 // 4 columns of each of 4 rows ({0-3,12-15,20-27}: rows 0,1,2,3 / columns 0-3,4-7,4-7,0-3), which is conflict-free
 // exactly when the row pitch is 8 slots (128 B) modulo 256 B next to the 9-slot record stride; rows are padded to that.
-#include "kernels.h"
+#include "igemm_halo_common.h"
 #include <algorithm>
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -95,13 +90,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
 
     // XCD-aware tile order (block b runs on XCD b % 8): contiguous runs of tiles per XCD, n-tile fastest
     const int tiles_n = p.Cout / BN;
-    int t;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    int t = xcd_first_tile(gridDim.x, blockIdx.x);
     const int tile_n = t % tiles_n;
     const int tile_m = t / tiles_n;
     const int n0 = tile_n * BN;
@@ -111,8 +100,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
     const float* gscale = p.scale;
     const float* gshift = p.shift;
     if (p.n_groups > 1) {
-        int g = 0;
-        while (g + 1 < p.n_groups && tile_m >= p.grp[g + 1].tile0) ++g;
+        const int g = group_of<&IgemmGroup::tile0>(p.grp, p.n_groups, tile_m);
         m0 = p.grp[g].row0 + (tile_m - p.grp[g].tile0) * 128;
         m_end = p.grp[g + 1].row0;
         gw = p.grp[g].w; gscale = p.grp[g].scale; gshift = p.grp[g].shift;
@@ -122,12 +110,10 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
 
     // ---- halo loader: float4 idx = tid + 256 j -> quad idx % 8 of halo pixel perm(idx / 8) (pairs of octets take pixels 4 records
     //      apart: conflict-free ds_write_b64, see igemm_halo.hip)
-    constexpr unsigned OOB = 0xFFFFFFF0u;
     int h_pix[HALO_PASSES];                     // pixel index of the halo pixel in plane (0, 0) / in the stride-1 tensor
     unsigned h_ok = 0;                          // validity: bit 4 j + plane (7 passes x 4 planes in one register)
-    unsigned h_dst2[(HALO_PASSES + 1) / 2];
-#pragma unroll
-    for (int j = 0; j < (HALO_PASSES + 1) / 2; ++j) h_dst2[j] = 0xFFFFFFFFu;
+    HaloDst<HALO_PASSES> h_dst;
+    h_dst.clear();
     const int per_sample = HPX * HPY;
 #pragma unroll
     for (int j = 0; j < HALO_PASSES; ++j) {
@@ -157,7 +143,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
         h_pix[j] = pix;
         h_ok |= ok << (4 * j);
         const unsigned dst = in_halo ? (unsigned)(s * SAMPLE_BYTES + hy * PITCH + hx * REC + q * 8) : 0xFFFFu;
-        h_dst2[j >> 1] = (j & 1) ? ((h_dst2[j >> 1] & 0x0000FFFFu) | (dst << 16)) : ((h_dst2[j >> 1] & 0xFFFF0000u) | dst);
+        h_dst.set(j, dst);
     }
     const int hq4 = (tid & 7) * 4;
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.seg[0].ptr, 0, p.seg_bytes[0], 0x00020000);
@@ -174,20 +160,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
             rh[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, off, 0, 0));
         }
     };
-    auto hstore = [&]() {
-#pragma unroll
-        for (int j = 0; j < HALO_PASSES; ++j) {
-            const unsigned dst = (j & 1) ? (h_dst2[j >> 1] >> 16) : (h_dst2[j >> 1] & 0xFFFFu);
-            if (dst == 0xFFFFu) continue;
-            const f32x4 v = rh[j];
-            const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-            fp16x2 l01, l23;          // residuals are exact in fp32; round them to nearest
-            l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-            l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
-            *reinterpret_cast<uint2*>(smem + dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-            *reinterpret_cast<uint2*>(smem + dst + 64) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-        }
-    };
+    auto hstore = [&]() { halo_store(smem, h_dst, rh); };
 
     // ---- weight loader: rows (tid >> 3) + 32 j of the n-tile, 16-byte segment (tid & 7); swizzled 128-byte rows
     const int lrow = tid >> 3;
@@ -312,16 +285,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo8_kernel(const IgemmParams p
                 const int row = r0 + it * RPP;
                 const int gy = row >> 3, gx = row & 7;
                 const size_t op = ((size_t)n * p.Hout + gy * p.os + p.oy) * p.Wout + gx * p.os + p.ox;
-                f32x4 v = *reinterpret_cast<const f32x4*>(Cs + row * CLD + c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
-                if (p.act == ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
-                } else if (p.act == ACT_LEAKY) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
-                }
+                const f32x4 v = bn_act4(*reinterpret_cast<const f32x4*>(Cs + row * CLD + c4), sc, sh, p.act, p.alpha);
                 amax = range_note4(amax, v);
                 *reinterpret_cast<f32x4*>(p.out + op * p.out_cstride + p.out_coff + col) = v;
             }

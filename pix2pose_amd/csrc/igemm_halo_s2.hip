@@ -11,15 +11,10 @@
 // sub-convolutions (2x2, 2x3, 3x2, 3x3 taps) accumulating into ONE output.  The K loop is (plane, slice, tap of the plane); per
 // (plane, slice) the (8 + 2) x (16 + 2) halo of the plane is staged once, addressed in the NHWC tensor directly; the weight panel
 // keeps its (tap, cin) order.
-#include "kernels.h"
+#include "igemm_halo_common.h"
 #include <algorithm>
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -67,13 +62,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo_s2_kernel(const IgemmParams
     // XCD-aware tile order (block b runs on XCD b % 8): contiguous runs of tiles per XCD, n-tile fastest
     const int tiles_n = p.Cout / BN;
     const int tiles_x = p.Wg / TX, tiles_y = p.Hg / TY;
-    int t;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    int t = xcd_first_tile(gridDim.x, blockIdx.x);
     const int tile_n = t % tiles_n;
     int tm = t / tiles_n;
     const int tx0 = (tm % tiles_x) * TX; tm /= tiles_x;
@@ -86,19 +75,16 @@ __global__ __launch_bounds__(256, 3) void igemm_halo_s2_kernel(const IgemmParams
     const float* gshift = p.shift;
     if (p.n_groups > 1) {                       // groups are runs of samples
         const int row = n * p.Hg * p.Wg;
-        int g = 0;
-        while (g + 1 < p.n_groups && p.grp[g + 1].row0 <= row) ++g;
+        const int g = group_of<&IgemmGroup::row0>(p.grp, p.n_groups, row);
         gw = p.grp[g].w; gscale = p.grp[g].scale; gshift = p.grp[g].shift;
     }
 
     // ---- halo loader: float4 idx = tid + 256 j -> quad idx % 8 of halo pixel perm(idx / 8) (igemm_halo.hip); the pixel index is
     //      that of plane (0, 0), the other planes add (py * Win + px); validity per plane in one bit each
-    constexpr unsigned OOB = 0xFFFFFFF0u;
     int h_pix[HALO_PASSES];
     unsigned h_ok = 0;                          // bit 4 j + plane
-    unsigned h_dst2[(HALO_PASSES + 1) / 2];
-#pragma unroll
-    for (int j = 0; j < (HALO_PASSES + 1) / 2; ++j) h_dst2[j] = 0xFFFFFFFFu;
+    HaloDst<HALO_PASSES> h_dst;
+    h_dst.clear();
 #pragma unroll
     for (int j = 0; j < HALO_PASSES; ++j) {
         const int idx = tid + 256 * j;
@@ -116,7 +102,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo_s2_kernel(const IgemmParams
         h_pix[j] = (n * p.Hin + iy) * p.Win + ix;
         h_ok |= ok << (4 * j);
         const unsigned dst = in_halo ? (unsigned)(hy * PITCH + hx * REC + q * 8) : 0xFFFFu;
-        h_dst2[j >> 1] = (j & 1) ? ((h_dst2[j >> 1] & 0x0000FFFFu) | (dst << 16)) : ((h_dst2[j >> 1] & 0xFFFF0000u) | dst);
+        h_dst.set(j, dst);
     }
     const int hq4 = (tid & 7) * 4;
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.seg[0].ptr, 0, p.seg_bytes[0], 0x00020000);
@@ -133,20 +119,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo_s2_kernel(const IgemmParams
             rh[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, off, 0, 0));
         }
     };
-    auto hstore = [&]() {
-#pragma unroll
-        for (int j = 0; j < HALO_PASSES; ++j) {
-            const unsigned dst = (j & 1) ? (h_dst2[j >> 1] >> 16) : (h_dst2[j >> 1] & 0xFFFFu);
-            if (dst == 0xFFFFu) continue;
-            const f32x4 v = rh[j];
-            const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-            fp16x2 l01, l23;          // residuals are exact in fp32; round them to nearest
-            l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-            l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
-            *reinterpret_cast<uint2*>(smem + dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-            *reinterpret_cast<uint2*>(smem + dst + 64) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-        }
-    };
+    auto hstore = [&]() { halo_store(smem, h_dst, rh); };
 
     // ---- weight loader: rows (tid >> 3) + 32 j of the n-tile, 16-byte segment (tid & 7); swizzled 128-byte rows
     const int lrow = tid >> 3;
@@ -269,16 +242,7 @@ __global__ __launch_bounds__(256, 3) void igemm_halo_s2_kernel(const IgemmParams
             const int row = h * 64 + r0 + it * RPP;
             const int gy = ty0 + (row >> 4), gx = tx0 + (row & 15);
             const size_t op = ((size_t)n * p.Hout + gy) * p.Wout + gx;
-            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
-            if (p.act == ACT_RELU) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
-            } else if (p.act == ACT_LEAKY) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
-            }
+            const f32x4 v = bn_act4(*reinterpret_cast<const f32x4*>(Cs + (r0 + it * RPP) * CLD + c4), sc, sh, p.act, p.alpha);
             amax = range_note4(amax, v);
             *reinterpret_cast<f32x4*>(p.out + op * p.out_cstride + p.out_coff + col) = v;
         }

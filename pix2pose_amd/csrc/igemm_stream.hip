@@ -17,38 +17,28 @@
 // its MFMA dependency rate (6 MFMAs per step) instead of one memory round trip per step.
 //
 // Operands: A = fp32 activations, gathered per lane straight from the NHWC tensor (row = lane & 31, 8 consecutive channels per
-// 16-deep block: two b128 loads) and split hi/lo in registers with the loaders' exact conversion (cvt_pkrtz, residual rounded
-// to nearest); B = the layer's pre-split weight panel, whose 128-byte K-step record [hi x32 | lo x32] of row (n0 + lane & 31)
-// is exactly the four b128 fragments a lane needs.  K-step order comes from a table (StreamOrder) describing the batched
+// 16-deep block: two b128 loads) and split hi/lo in registers by the loaders' own split4() (device_common.h); B = the
+// layer's pre-split weight panel, whose 128-byte K-step record [hi x32 | lo x32] of row (n0 + lane & 31) is exactly the four b128 fragments a lane needs.  K-step order comes from a table (StreamOrder) describing the batched
 // kernel's loop nest: groups of taps, and inside a group (channel slice, tap).
-#include "kernels.h"
+#include "device_common.h"
 #include <cstdlib>
 
 namespace p2p {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr unsigned OOB = 0x80000000u;          // every tensor on this path is < 2 GB (igemm_stream_supported)
+constexpr unsigned STREAM_OOB = 0x80000000u;   // every tensor on this path is < 2 GB (igemm_stream_supported): not the shared OOB
 constexpr int MAX_STEPS = 512;                 // K-steps of one launch (conv4: 400)
 
-// hi/lo split of 8 consecutive fp32 values, as hstore() / lstore() of the batched kernels do it
+// hi/lo split of 8 consecutive fp32 values into one MFMA fragment each: two split4()
 __device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, f16x8& hi, f16x8& lo)
 {
-    const fp16x2 h0 = __builtin_amdgcn_cvt_pkrtz(a[0], a[1]), h1 = __builtin_amdgcn_cvt_pkrtz(a[2], a[3]);
-    const fp16x2 h2 = __builtin_amdgcn_cvt_pkrtz(b[0], b[1]), h3 = __builtin_amdgcn_cvt_pkrtz(b[2], b[3]);
-    fp16x2 l0, l1, l2, l3;          // residuals are exact in fp32; round them to nearest
-    l0[0] = (__fp16)(a[0] - (float)h0[0]); l0[1] = (__fp16)(a[1] - (float)h0[1]);
-    l1[0] = (__fp16)(a[2] - (float)h1[0]); l1[1] = (__fp16)(a[3] - (float)h1[1]);
-    l2[0] = (__fp16)(b[0] - (float)h2[0]); l2[1] = (__fp16)(b[1] - (float)h2[1]);
-    l3[0] = (__fp16)(b[2] - (float)h3[0]); l3[1] = (__fp16)(b[3] - (float)h3[1]);
+    uint2 ha, la, hb, lb;
+    split4(a, ha, la);
+    split4(b, hb, lb);
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 hv = {__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1), __builtin_bit_cast(unsigned, h2), __builtin_bit_cast(unsigned, h3)};
-    const u32x4 lv = {__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1), __builtin_bit_cast(unsigned, l2), __builtin_bit_cast(unsigned, l3)};
+    const u32x4 hv = {ha.x, ha.y, hb.x, hb.y};
+    const u32x4 lv = {la.x, la.y, lb.x, lb.y};
     hi = __builtin_bit_cast(f16x8, hv);
     lo = __builtin_bit_cast(f16x8, lv);
 }
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(64) void igemm_stream_kernel(const IgemmParams p, c
         const int koff = w1 & 0x00FFFFFF;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const unsigned off = (live && (a_mask[i] & bit)) ? (s1 ? a_off1[i] : a_off0[i]) + (unsigned)a_toff : OOB;
+            const unsigned off = (live && (a_mask[i] & bit)) ? (s1 ? a_off1[i] : a_off0[i]) + (unsigned)a_toff : STREAM_OOB;
             if (s1) {
                 ra[s][i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a1, off, 0, 0));
                 ra[s][i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a1, off + 16, 0, 0));
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(64) void igemm_stream_kernel(const IgemmParams p, c
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const unsigned off = live ? b_off[j] + (unsigned)koff : OOB;
+            const unsigned off = live ? b_off[j] + (unsigned)koff : STREAM_OOB;
             rb[s][j][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, off, 0, 0));          // hi, k block 0
             rb[s][j][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, off + 64, 0, 0));     // lo, k block 0
             rb[s][j][2] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_w, off + 32, 0, 0));     // hi, k block 1
@@ -249,9 +239,7 @@ __global__ __launch_bounds__(64) void igemm_stream_kernel(const IgemmParams p, c
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 if (ops[r] < 0) continue;
-                float v = fmaf(acc[i][j][r], sc, sh) + rs[r];
-                if (p.act == ACT_RELU) v = relu_nan(v);
-                else if (p.act == ACT_LEAKY) v = v > 0.f ? v : v * p.alpha;
+                const float v = bn_act1(acc[i][j][r], sc, sh, rs[r], p.act, p.alpha);
                 amax = range_note1(amax, v);
                 p.out[(size_t)ops[r] * p.out_cstride + p.out_coff + col] = v;
             }

@@ -1,5 +1,5 @@
 // Small non-GEMM kernels of the generator forward pass (gfx950).
-#include "kernels.h"
+#include "device_common.h"
 
 namespace p2p {
 
@@ -75,10 +75,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const float* __restrict
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int co = cg * CPT + c + e;
-            float t = fmaf(acc[c + e], scale[co], shift[co]);
-            if (act == ACT_RELU) t = relu_nan(t);
-            else if (act == ACT_LEAKY) t = t > 0.f ? t : t * alpha;
-            v[e] = t;
+            v[e] = bn_act1(acc[c + e], scale[co], shift[co], act, alpha);
         }
         *reinterpret_cast<float4*>(op + c) = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -111,8 +108,7 @@ __global__ void maxpool3s2_kernel(const float* __restrict__ x, int N, int H, int
     // Workgroup b runs on XCD b % 8 and each XCD has its own L2: give every XCD a contiguous run of output (whole images), so that
     // the input rows two output rows share are re-read from the SAME L2 (in launch order the two rows sat on different XCDs and
     // the kernel fetched 1.5x its input).
-    const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const unsigned lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const unsigned lb = (unsigned)xcd_first_tile(gridDim.x, blockIdx.x);
     for (size_t i = (size_t)lb * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % C4);
         size_t r = i / C4;

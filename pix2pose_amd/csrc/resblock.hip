@@ -17,7 +17,7 @@
 //
 // Bits: every output element is the same chain of v_mfma_f32_32x32x16_f16 over the same K-step order as in the three-launch route -- 2a:
 // slices in order; 2b: (slice, tap); 2c: slices in order; (al bh, ah bl, ah bh) inside a step; the same epilogue expressions; the same
-// cvt_pkrtz / round-to-nearest split of the fp32 intermediate -- so the routes agree bit for bit (tests/test_resblock_gpu.py), and a
+// split4() of the fp32 intermediate (device_common.h) -- so the routes agree bit for bit (tests/test_resblock_gpu.py), and a
 // detection's bits do not depend on the batch it travels in (small launches keep the streaming route).  Phases A and B run the MFMA in
 // transposed orientation (weights as the row operand): a lane then owns 4 consecutive channels of one pixel and the split image is
 // written with 8-byte stores; swapping the operand roles changes no bit.
@@ -26,33 +26,16 @@
 //         F1 = 128 (res3: 16x16x512): 4 x 16 patch, 6 x 16 halo -- the image is one patch wide, so the columns left and right of it are
 //                  padding: lanes whose tap falls there read a zero record instead of a halo column --, LDS 71.8 KB
 // Two workgroups per CU either way (their phases interleave: one's memory-bound phase A under the other's MFMA-bound phase B).
-#include "kernels.h"
+#include "device_common.h"
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int REC = 144;        // activation record: [hi f16 x32 | lo f16 x32 | 16 B pad] (igemm_halo.hip)
 constexpr int WREC = 128;       // weight row of a K-step: [hi x32 | lo x32], 16-byte chunk c of row r at c ^ ((r >> 1) & 7)
-constexpr unsigned OOB = 0xFFFFFFF0u;
 
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
-
-// hi = f16(v) toward zero (cvt_pkrtz), lo = f16(v - hi) to nearest: the loaders' split (igemm.hip lstore, igemm_halo.hip hstore)
-__device__ __forceinline__ void split4(const f32x4 v, uint2& hi, uint2& lo)
-{
-    const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), h23 = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-    fp16x2 l01, l23;
-    l01[0] = (__fp16)(v[0] - (float)h01[0]); l01[1] = (__fp16)(v[1] - (float)h01[1]);
-    l23[0] = (__fp16)(v[2] - (float)h23[0]); l23[1] = (__fp16)(v[3] - (float)h23[1]);
-    hi = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-    lo = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-}
 
 // DA / DB: K-steps of global loads in flight in phases A / B (register rings).  A K-step of these phases is 12 - 18 MFMAs per wave -- a few
 // hundred cycles, a fraction of a loaded memory round trip -- so with the usual one-step-ahead prefetch every step waited for its operands.
@@ -128,18 +111,14 @@ __global__ __launch_bounds__(256, 2) void resblock_kernel(const ResBlockParams p
 
     // XCD-aware tile order (block b runs on XCD b % 8): contiguous runs of patches per XCD
     const int tiles_x = p.W / 16, tiles_y = p.H / PY;
-    int t;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    int t = xcd_first_tile(gridDim.x, blockIdx.x);
     const int x0 = (t % tiles_x) * 16; t /= tiles_x;
     const int y0 = (t % tiles_y) * PY;
     const int n = t / tiles_y;
 
-    int g = 0;                                   // mixed-object batches: groups are runs of samples
+    // mixed-object batches: groups are runs of samples (group_of, device_common.h, written out: as a call the register allocation of this
+    // kernel moved)
+    int g = 0;
     while (g + 1 < p.n_groups && p.grp[g + 1].sample0 <= n) ++g;
     // [s2a F1 | h2a F1 | s2b F1 | h2b F1 | s2c C | h2c C]: fetched once (a global load per use put a memory round trip in front of every
     // group of four channels in the epilogues)
@@ -351,6 +330,7 @@ __global__ __launch_bounds__(256, 2) void resblock_kernel(const ResBlockParams p
                 const int c = ntA * 32 + 8 * gq + 4 * lk;
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(ss + c);
                 const f32x4 sh = *reinterpret_cast<const f32x4*>(ss + F1 + c);
+                // (bn_act4 of device_common.h with a fixed ReLU, written out: as a call this kernel's register allocation moved)
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = relu_nan(fmaf(accA[i][4 * gq + e], sc[e], sh[e]));
@@ -528,6 +508,7 @@ __global__ __launch_bounds__(256, 2) void resblock_kernel(const ResBlockParams p
                 const int c = ntB * 32 + 8 * gq + 4 * lk;
                 const f32x4 sc = *reinterpret_cast<const f32x4*>(ss + 2 * F1 + c);
                 const f32x4 sh = *reinterpret_cast<const f32x4*>(ss + 3 * F1 + c);
+                // (bn_act4 of device_common.h with a fixed ReLU, written out: as a call this kernel's register allocation moved)
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = relu_nan(fmaf(accB[i][4 * gq + e], sc[e], sh[e]));
@@ -662,6 +643,7 @@ __global__ __launch_bounds__(256, 2) void resblock_kernel(const ResBlockParams p
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (r0 + 8 * it) * CLD + c4);
+                    // (bn_act4 of device_common.h with a fixed ReLU, written out: as a call this kernel's register allocation moved)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = relu_nan(fmaf(v[e], sc[e], sh[e]) + 0.f);      // igemm.hip's epilogue with no residual: + 0
                     amax = range_note4(amax, v);
@@ -789,6 +771,7 @@ __global__ __launch_bounds__(256, 2) void resblock_kernel(const ResBlockParams p
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     f32x4 v = *reinterpret_cast<const f32x4*>(Cs + (r0 + 8 * it) * CLD + c4);
+                    // (bn_act4 with a residual, device_common.h, fixed ReLU, written out: as a call this kernel's register allocation moved)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaf(v[e], sc[e], sh[e]);
 #pragma unroll

@@ -25,22 +25,11 @@
 //                       and stays in the L2 of the XCDs that work on that tile), 24 MFMAs.  The V image of the next slice is copied
 //                       global -> registers -> LDS two pieces per K-step into the second buffer: one barrier per slice.  Epilogue:
 //                       the eight positions meet in LDS (four passes of 32 pairs), inverse transform, BN + LeakyReLU, 256-byte stores.
-#include "kernels.h"
+#include "wino_common.h"
 
 namespace p2p {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-constexpr unsigned OOB = 0xFFFFFFF0u;
-
-// Workgroup barrier for LDS traffic only: __syncthreads() carries a release fence, which on gfx950 is s_waitcnt vmcnt(0) -- every global
-// STORE of the epilogue would have to reach L2 before the next exchange pass (and, in the persistent loop, before the next tile) could start.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // input transform.  Thread = (row of an 8-row block, tile t of the 16-column patch, channel quad of a 32-channel group); quads fastest, so
@@ -97,12 +86,10 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoParams p)
     for (int j = 0; j < 8; ++j) {
         const f32x4 w = v[j];
         amax = range_note4(amax, w);
-        const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(w[0], w[1]), h23 = __builtin_amdgcn_cvt_pkrtz(w[2], w[3]);
-        fp16x2 l01, l23;              // residuals are exact in fp32; round them to nearest
-        l01[0] = (__fp16)(w[0] - (float)h01[0]); l01[1] = (__fp16)(w[1] - (float)h01[1]);
-        l23[0] = (__fp16)(w[2] - (float)h23[0]); l23[1] = (__fp16)(w[3] - (float)h23[1]);
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+        uint2 hi, lo;
+        split4(w, hi, lo);
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * plane_bytes) = hi;
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * plane_bytes) = lo;
     }
     range_commit(p.range_acc, amax);       // the transformed operand is what the split sees: up to 15x the activation
 }
@@ -146,13 +133,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(const WinoParams p)
 
     // XCD-aware order (block b runs on XCD b % 8): every sweep of gridDim.x tiles is cut into contiguous runs per XCD, channel tile fastest:
     // the workgroups that share a V patch (one per channel tile) run on one XCD at the same time
-    int tl0;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        tl0 = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tl0 = xcd_first_tile(gridDim.x, blockIdx.x);
     const int pair = tid >> 4, cq = tid & 15;       // epilogue role
     float amax = 0.f;
 
@@ -172,13 +153,10 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(const WinoParams p)
     const float* gscale = p.scale;
     const float* gshift = p.shift;
     if (p.n_groups > 1) {                            // groups are runs of samples; DUAL: every group is paired up on its own (unit0)
-        int g = 0;
+        const int g = DUAL ? group_of<&WinoGroup::unit0>(p.grp, p.n_groups, unit) : group_of<&WinoGroup::sample0>(p.grp, p.n_groups, n0);
         if (DUAL) {
-            while (g + 1 < p.n_groups && p.grp[g + 1].unit0 <= unit) ++g;
             n0 = p.grp[g].sample0 + 2 * (unit - p.grp[g].unit0);
             n_end = p.grp[g + 1].sample0;
-        } else {
-            while (g + 1 < p.n_groups && p.grp[g + 1].sample0 <= n0) ++g;
         }
         gu = p.grp[g].U; gscale = p.grp[g].scale; gshift = p.grp[g].shift;
     }
@@ -354,13 +332,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(const WinoParams p)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         float* X = reinterpret_cast<float*>(smem + (i & 1) * XBUF);
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = {acc[c][i][4 * q], acc[c][i][4 * q + 1], acc[c][i][4 * q + 2], acc[c][i][4 * q + 3]};
-                *reinterpret_cast<f32x4*>(X + (j * 32 + li) * XLD + c * 32 + 8 * q + 4 * lk) = v;
-            }
+        exchange_store<XLD>(X, j, li, lk, acc[0][i], acc[1][i]);
         lds_barrier();
         f32x4 m[8];
 #pragma unroll
@@ -391,16 +363,7 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_kernel(const WinoParams p)
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                f32x4 v = yv[k];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(v[e], sc[e], sh[e]);
-                if (p.act == ACT_RELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
-                } else if (p.act == ACT_LEAKY) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
-                }
+                const f32x4 v = bn_act4(yv[k], sc, sh, p.act, p.alpha);
                 amax = range_note4(amax, v);
 #ifdef P2P_ABL_WST
                 if (v[0] == 123.456f)

@@ -26,16 +26,11 @@
 //                       per slice, py = 1 three -- the phase a workgroup serves rotates with the sweep so that every CU gets the same mix.
 //                       (First form, measured equal: wave = (position, 32-channel half) sharing the planes of a position through a
 //                       workgroup barrier per slice; timing ablations of both: tools/experiments/README.md.)
-#include "kernels.h"
+#include "wino_common.h"
 
 #include <type_traits>
 
 namespace p2p {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 #ifdef P2P_W3_STAMPS      // A/B builds: 100 MHz time stamps of the phases of a workgroup's tiles (tools/w3_stamps.py)
 __device__ unsigned long long g_w3_stamps[8 * 16 * 16];
@@ -46,10 +41,6 @@ __device__ unsigned long long g_w3_stamps[8 * 16 * 16];
 #endif
 
 namespace {
-
-constexpr unsigned OOB = 0xFFFFFFF0u;
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // input transform.  Thread = (row of an 8-row block, tile t of the 16-column patch, channel quad of a 32-channel group), quads fastest.
@@ -80,17 +71,7 @@ __global__ __launch_bounds__(256) void wino3_input_kernel(const Wino3Params p)
         d[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
     }
     f32x4 v[6];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float d0 = d[0][e], d1 = d[1][e], d2 = d[2][e], d3 = d[3][e], d4 = d[4][e], d5 = d[5][e];
-        // BT of F(4,3) at {0, 1, -1, 2, -2, inf}: integer coefficients, the order of operations is fixed
-        const float a12 = __builtin_fmaf(-4.f, d2, d4), b12 = __builtin_fmaf(-4.f, d1, d3);
-        const float a34 = d4 - d2, b34 = 2.f * (d3 - d1);
-        v[0][e] = __builtin_fmaf(4.f, d0, __builtin_fmaf(-5.f, d2, d4));
-        v[1][e] = a12 + b12; v[2][e] = a12 - b12;
-        v[3][e] = a34 + b34; v[4][e] = a34 - b34;
-        v[5][e] = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-    }
+    f43_input_transform(d, v);
     const int S = p.Cin >> 4;
     const int slice = cg * 2 + (quad >> 2), lk = (quad >> 1) & 1;
     const size_t plane_bytes = (size_t)p.H * 64;
@@ -100,12 +81,10 @@ __global__ __launch_bounds__(256) void wino3_input_kernel(const Wino3Params p)
     for (int j = 0; j < 6; ++j) {
         const f32x4 w = v[j];
         amax = range_note4(amax, w);
-        const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(w[0], w[1]), h23 = __builtin_amdgcn_cvt_pkrtz(w[2], w[3]);
-        fp16x2 l01, l23;              // residuals are exact in fp32; round them to nearest
-        l01[0] = (__fp16)(w[0] - (float)h01[0]); l01[1] = (__fp16)(w[1] - (float)h01[1]);
-        l23[0] = (__fp16)(w[2] - (float)h23[0]); l23[1] = (__fp16)(w[3] - (float)h23[1]);
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * plane_bytes) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+        uint2 hi, lo;
+        split4(w, hi, lo);
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * plane_bytes) = hi;
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * plane_bytes) = lo;
     }
     range_commit(p.range_acc, amax);       // the transformed operand is what the split sees: up to 10x the activation
 }
@@ -154,13 +133,7 @@ __global__ __launch_bounds__(NU * 384, 2 / NU) void wino3_gemm_kernel(const Wino
 
     // XCD-aware order (block b runs on XCD b % 8): every sweep of gridDim.x tiles is cut into contiguous runs per XCD, the tiles of one
     // patch next to each other: the workgroups that share a V patch run on one XCD at the same time
-    int tl0;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        tl0 = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tl0 = xcd_first_tile(gridDim.x, blockIdx.x);
     const int cq = tid & 15;                         // epilogue role: (pair = role >> 4, channel quad), roles 0..511
     float amax = 0.f;
     char* const wimg = smem + wv * WIMG;             // this wave's image in buffer 0
@@ -185,6 +158,7 @@ __global__ __launch_bounds__(NU * 384, 2 / NU) void wino3_gemm_kernel(const Wino
     const float* gu = p.U;
     const float* gscale = p.scale;
     const float* gshift = p.shift;
+    // (group_of, device_common.h, written out: as a call the register allocation of this kernel moved)
     if (NU == 1) {
         tn0 = wunit / UPS; ty0 = (wunit % UPS) * 16;
         if (p.n_groups > 1) {
@@ -363,13 +337,7 @@ __global__ __launch_bounds__(NU * 384, 2 / NU) void wino3_gemm_kernel(const Wino
     for (int i = 0; i < 2; ++i) {
         if (i) lds_barrier();                        // pass 0's images have been read
         float* Xw = reinterpret_cast<float*>(smem + mh * XBUF);
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = {acc[i][c][4 * q], acc[i][c][4 * q + 1], acc[i][c][4 * q + 2], acc[i][c][4 * q + 3]};
-                *reinterpret_cast<f32x4*>(Xw + (j * 32 + li) * XLD + c * 32 + 8 * q + 4 * lk) = v;
-            }
+        exchange_store<XLD>(Xw, j, li, lk, acc[i][0], acc[i][1]);
         lds_barrier();
         for (int role = tid; role < 512; role += NTHR) {
             const int pair = role >> 4;
@@ -387,19 +355,10 @@ __global__ __launch_bounds__(NU * 384, 2 / NU) void wino3_gemm_kernel(const Wino
                     const size_t pix = ((size_t)n * (2 * p.H) + (2 * y + py)) * (2 * p.W) + 2 * (pc * 16 + (pair & 3) * 4) + px;
                     float* o = p.out + pix * p.out_cstride + p.out_coff + col;
                     f32x4 yv[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // AT of F(4,3): rows (1 1 1 1 1 0), (0 1 -1 2 -2 0), (0 1 1 4 4 0), (0 1 -1 8 -8 1)
-                        const float s12 = m[1][e] + m[2][e], d12 = m[1][e] - m[2][e];
-                        const float s34 = m[3][e] + m[4][e], d34 = m[3][e] - m[4][e];
-                        yv[0][e] = (m[0][e] + s12) + s34;
-                        yv[1][e] = __builtin_fmaf(2.f, d34, d12);
-                        yv[2][e] = __builtin_fmaf(4.f, s34, s12);
-                        yv[3][e] = __builtin_fmaf(8.f, d34, d12) + m[5][e];
-                    }
+                    f43_inverse(m, yv);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        f32x4 v = yv[k];
+                        f32x4 v = yv[k];             // bn_act4 (device_common.h) written out: as a call this kernel's scratch use moved
 #pragma unroll
                         for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(v[e], sc[e], sh[e]);
                         if (p.act == ACT_RELU) {

@@ -16,26 +16,19 @@
 // V layout (input transform -> GEMM): [unit of 8 samples][K slice][plane = (j, hi/lo, k half)][sample 8][row 8][tile 2][8 halves]; K slice =
 // 16-channel slice (MODE 0) or (parity plane, 16-channel slice) (MODE 1).  LDS image of a K slice: 24 planes of [sample 8][10 rows: zero, the
 // 8 rows, zero][tile 2][16 B]; m-tile i = samples 2i, 2i + 1; a vertical tap is a constant byte shift (32 B per row).
-#include "kernels.h"
+#include "wino_common.h"
 
 #include <type_traits>
 
 namespace p2p {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-constexpr unsigned OOB = 0xFFFFFFF0u;
 constexpr unsigned VPLANE = 2048;                   // bytes of one V plane in HBM: 8 samples x 8 rows x 2 tiles x 16 B
 constexpr unsigned VSLICE = 24 * VPLANE;
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // unit (group of eight samples of one object) and slot of sample n
+// (group_of, device_common.h, written out: as a call the register allocation of the kernels of this file moved)
 __device__ __forceinline__ void unit_of(const Wino3oParams& p, int n, int& unit, int& slot)
 {
     if (p.n_groups > 1) {
@@ -88,17 +81,7 @@ __global__ __launch_bounds__(256) void wino3o_input_kernel(const Wino3oParams p)
     }
     if (n >= p.N) return;
     f32x4 v[6];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float d0 = d[0][e], d1 = d[1][e], d2 = d[2][e], d3 = d[3][e], d4 = d[4][e], d5 = d[5][e];
-        // BT of F(4,3) at {0, 1, -1, 2, -2, inf}, the same expressions as wino3_input_kernel
-        const float a12 = __builtin_fmaf(-4.f, d2, d4), b12 = __builtin_fmaf(-4.f, d1, d3);
-        const float a34 = d4 - d2, b34 = 2.f * (d3 - d1);
-        v[0][e] = __builtin_fmaf(4.f, d0, __builtin_fmaf(-5.f, d2, d4));
-        v[1][e] = a12 + b12; v[2][e] = a12 - b12;
-        v[3][e] = a34 + b34; v[4][e] = a34 - b34;
-        v[5][e] = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-    }
+    f43_input_transform(d, v);
     int unit, slot;
     unit_of(p, n, unit, slot);
     const int lk = (quad >> 1) & 1;
@@ -109,12 +92,10 @@ __global__ __launch_bounds__(256) void wino3o_input_kernel(const Wino3oParams p)
     for (int j = 0; j < 6; ++j) {
         const f32x4 w = v[j];
         amax = range_note4(amax, w);
-        const fp16x2 h01 = __builtin_amdgcn_cvt_pkrtz(w[0], w[1]), h23 = __builtin_amdgcn_cvt_pkrtz(w[2], w[3]);
-        fp16x2 l01, l23;
-        l01[0] = (__fp16)(w[0] - (float)h01[0]); l01[1] = (__fp16)(w[1] - (float)h01[1]);
-        l23[0] = (__fp16)(w[2] - (float)h23[0]); l23[1] = (__fp16)(w[3] - (float)h23[1]);
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * VPLANE) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * VPLANE) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+        uint2 hi, lo;
+        split4(w, hi, lo);
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4) * VPLANE) = hi;
+        *reinterpret_cast<uint2*>(dst + (size_t)(j * 4 + 2) * VPLANE) = lo;
     }
     range_commit(p.range_acc, amax);
 }
@@ -153,13 +134,7 @@ __global__ __launch_bounds__(768) void wino3o_gemm_kernel(const Wino3oParams p)
     const int ntiles = units * G4;
     const size_t unit_block = (size_t)(MODE == 0 ? S : 4 * S) * VSLICE;
 
-    int tl0;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int xcd = b & 7, idx = b >> 3;
-        tl0 = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tl0 = xcd_first_tile(gridDim.x, blockIdx.x);
     const int pair = tid >> 4, cq = tid & 15;       // epilogue role (threads 0..511)
     float amax = 0.f;
     char* const wimg = smem + wv * 2 * WIMG;         // this wave's image in buffer 0
@@ -296,7 +271,7 @@ __global__ __launch_bounds__(768) void wino3o_gemm_kernel(const Wino3oParams p)
     }
     lds_barrier();                                   // every wave is done with its image: the exchange images may overwrite them
 
-    // ---- epilogue (see wino3.hip).  Pass i: every wave puts m-tile i of its four samples into exchange image mh; pair = sample
+    // ---- epilogue (pass structure as in wino3.hip).  Pass i: every wave puts m-tile i of its four samples into exchange image mh; pair = sample
     //      4 im + 2 i + (pair >> 4), row (pair >> 1) & 7, tile pair & 1 of image im.
     const int col = ntile * 64 + cq * 4;
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -309,13 +284,7 @@ __global__ __launch_bounds__(768) void wino3o_gemm_kernel(const Wino3oParams p)
     for (int i = 0; i < 2; ++i) {
         if (i) lds_barrier();                        // pass 0's images have been read
         float* Xw = reinterpret_cast<float*>(smem + mh * XBUF);
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = {acc[i][c][4 * q], acc[i][c][4 * q + 1], acc[i][c][4 * q + 2], acc[i][c][4 * q + 3]};
-                *reinterpret_cast<f32x4*>(Xw + (j * 32 + li) * XLD + c * 32 + 8 * q + 4 * lk) = v;
-            }
+        exchange_store<XLD>(Xw, j, li, lk, acc[i][0], acc[i][1]);
         lds_barrier();
         if (tid < 512) {
 #pragma unroll
@@ -341,28 +310,12 @@ __global__ __launch_bounds__(768) void wino3o_gemm_kernel(const Wino3oParams p)
                     ostep = (size_t)p.out_cstride;
                 }
                 f32x4 yv[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float s12 = m[1][e] + m[2][e], d12 = m[1][e] - m[2][e];
-                    const float s34 = m[3][e] + m[4][e], d34 = m[3][e] - m[4][e];
-                    yv[0][e] = (m[0][e] + s12) + s34;
-                    yv[1][e] = __builtin_fmaf(2.f, d34, d12);
-                    yv[2][e] = __builtin_fmaf(4.f, s34, s12);
-                    yv[3][e] = __builtin_fmaf(8.f, d34, d12) + m[5][e];
-                }
+                f43_inverse(m, yv);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     f32x4 v = yv[k];
                     if (!raw) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(v[e], sc[e], sh[e]);
-                        if (p.act == ACT_RELU) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
-                        } else if (p.act == ACT_LEAKY) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * p.alpha;
-                        }
+                        v = bn_act4(v, sc, sh, p.act, p.alpha);
                         amax = range_note4(amax, v);
                     }
                     *reinterpret_cast<f32x4*>(o + (size_t)k * ostep) = v;
