@@ -675,6 +675,74 @@ P2P_API int p2p_xyz_rotate_patch_batch(p2p_ctx* ctx, const unsigned char* const*
                                        const float* rgb_table, const float* xyz_table, int resize_generation, unsigned char* patches,
                                        int* shapes);
 
+/* ------------------------------------------------------------------------------------------
+ * Training batches (reference pix2pose_util/data_io.py:53-274, get_patch_pair).  csrc/train_batch.hip; DESIGN.md section 8.5.
+ * ---------------------------------------------------------------------------------------- */
+
+#define P2P_TRAIN_MAX_PATCH 128      /* rows and columns of a train_xyz patch (make_train_xyz's resize rule) */
+#define P2P_TRAIN_MAX_WINDOW 250     /* side of the crop window, 2 * int(max(w', h') * 1.5 / 2) with w', h' <= 1.3 * 128 */
+
+/* p2p_train_batch's status per sample */
+#define P2P_TRAIN_OK 0
+#define P2P_TRAIN_BAD_PATCH (-1)        /* null, not 6 or 7 channels, a side of 0 or above P2P_TRAIN_MAX_PATCH */
+#define P2P_TRAIN_BAD_BACKGROUND (-2)   /* null, not 1 or 3 channels, or after the enlargement rule smaller than the patch plus 20 */
+#define P2P_TRAIN_BAD_DRAW (-3)         /* a value that is not finite, a paste or window outside the frame, a window above the bound */
+
+/* What one sample's draws of the `random` module come to, every int(...) taken on the host (runtime.train_draws).  The frame is the
+ * background after the enlargement rule (:78-85): max(H, 2 h) x max(W, 2 w) where H < 2 h or W < 2 w, else H x W. */
+typedef struct p2p_train_draw {
+    int v_ref, u_ref;       /* where the patch is pasted (:90-91) */
+    int v1, v2, u1, u2;     /* the crop window clipped to the frame (:120-154): rows v1 .. v2, columns u1 .. u2 */
+    int side;               /* side of the unclipped window = of base_image (:125) */
+    int shift_v, shift_u;   /* shift_v_min, shift_u_min: where the clipped window starts in base_image (:140-150) */
+    int rect[3][4];         /* first occlusion (:164), second occlusion (:233), background inclusion (:247): rows r0 .. r1 and columns
+                               c0 .. c1 of the frame with Python's slice rule already applied; r0 >= r1 or c0 >= c1: none */
+    int even;               /* batch_count % 2 == 0 (:203) */
+    int reserved;
+    double sigma_edge;      /* :191, the boundary's Gaussian (applied as a dilation) */
+    double sigma_blur;      /* :193, the image blur */
+    double sigma_ran;       /* :206, clamped to [0.1, 1]; unused when even == 0 */
+    double rot[6];          /* rows 0 and 1 of rotate(angle)'s map (x, y, 1) of the output -> (column, row) of base_image (:264-268) */
+} p2p_train_draw;
+
+/* Parameters of the colour stage (seq_syn, :42-51) for one sample; see p2p_train_batch.  order: a permutation of 0 .. 7 =
+ * Add on channel 0, 1, 2; ContrastNormalization; Multiply; GaussianBlur; AdditiveGaussianNoise; the second ContrastNormalization. */
+typedef struct p2p_train_colour {
+    int order[8];
+    float add[3];
+    float contrast;
+    float mul[3];
+    float blur_sigma;
+    float noise_scale;      /* 0: the Sometimes(0.1, ...) did not fire */
+    float contrast2[3];     /* 1, 1, 1: the Sometimes(0.5, ...) did not fire */
+    unsigned int sample;    /* the noise generator's key is (seed, sample, pixel, channel) */
+    unsigned long long seed;
+} p2p_train_colour;
+
+/* sizeof of the records above for a binding's self-check: 0 = p2p_train_draw, 1 = p2p_train_colour, else -1 */
+P2P_API int p2p_train_sizeof(int which);
+
+/* n training samples in one call: get_patch_pair of scikit-image 0.17 / 0.18 (generation must be 1) from explicit draws.
+ * Sample k: patches[k] host u8 [h][w][c] with patch_shapes[k] = (h, w, c), c = 6 or 7 (rgb, xyz, and an unused visibility channel),
+ * h, w <= P2P_TRAIN_MAX_PATCH; backgrounds[k] host u8 [H][W][C] with back_shapes[k] = (H, W, C), C = 3 or 1 (grey, replicated);
+ * draws[k]; colours[k] when colours is not null (null: the colour stage is skipped, which is the reference with an augmenter that
+ * returns its input).  Only the background under the window travels to the device.  Stages as DESIGN.md section 8.5 lists them:
+ * enlargement of a small background (float32 warp), compositing, first occlusion, boundary by np.gradient's differences, the two
+ * thresholded Gaussians as square dilations of radius int(4 sigma + 0.5), the separable blurs with scipy's weights and
+ * mode='nearest', the even-batch branch with its radius > 0.3 test in double, normalisation to [-1, 1], placement, rotation
+ * (base and target 'reflect', mask 'constant') and the resize to imsize x imsize (anti-aliased, 'reflect') in double.
+ * The colour stage works on the 0 .. 255 float patch, clips to [0, 255] after every augmenter, blurs with mirrored edges, and is a
+ * restatement of imgaug's documented meaning, not pinned to it.
+ * src, tgt: float32 [n][imsize][imsize][3]; mask: float32 [n][imsize][imsize]; host memory (out_mem = P2P_MEM_HOST) or device
+ * memory of the context's device (P2P_MEM_DEVICE); complete when the call returns.  16 <= imsize <= 512.
+ * status [n] (host): P2P_TRAIN_OK or the reason the sample was left out (its outputs are 0, p2p_last_error names the first such
+ * sample); the other samples are not affected, and a sample's result is bit-identical alone or in a batch.  Returns
+ * P2P_ERR_INVALID_ARG only for null arguments, a bad imsize or generation. */
+P2P_API int p2p_train_batch(p2p_ctx* ctx, int n, const unsigned char* const* patches, const int* patch_shapes,
+                            const unsigned char* const* backgrounds, const int* back_shapes, const p2p_train_draw* draws,
+                            const p2p_train_colour* colours, int imsize, int generation, float* src, float* tgt, float* mask, int out_mem,
+                            int* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,22 @@ class RefineResult(C.Structure):
     _fields_ = [("input", IcpInput), ("icp", IcpResult), ("R", C.c_double * 9), ("t", C.c_double * 3), ("score", DepthScore)]
 
 
+class TrainDraw(C.Structure):
+    _fields_ = [("v_ref", C.c_int), ("u_ref", C.c_int), ("v1", C.c_int), ("v2", C.c_int), ("u1", C.c_int), ("u2", C.c_int),
+                ("side", C.c_int), ("shift_v", C.c_int), ("shift_u", C.c_int), ("rect", (C.c_int * 4) * 3), ("even", C.c_int),
+                ("reserved", C.c_int), ("sigma_edge", C.c_double), ("sigma_blur", C.c_double), ("sigma_ran", C.c_double),
+                ("rot", C.c_double * 6)]
+
+
+class TrainColour(C.Structure):
+    _fields_ = [("order", C.c_int * 8), ("add", C.c_float * 3), ("contrast", C.c_float), ("mul", C.c_float * 3),
+                ("blur_sigma", C.c_float), ("noise_scale", C.c_float), ("contrast2", C.c_float * 3), ("sample", C.c_uint),
+                ("seed", C.c_uint64)]
+
+
+TRAIN_MAX_PATCH, TRAIN_MAX_WINDOW = 128, 250                       # P2P_TRAIN_MAX_PATCH, P2P_TRAIN_MAX_WINDOW
+TRAIN_OK, TRAIN_BAD_PATCH, TRAIN_BAD_BACKGROUND, TRAIN_BAD_DRAW = 0, -1, -2, -3     # p2p_train_batch's status per sample
+
 ERR_CAPACITY = -4
 ICP_OK, ICP_SMALL_BBOX, ICP_FEW_POINTS = 0, -1, -2     # p2p_icp_input.status; both nonzero values are the reference's -1
 ICP_NONFINITE = -3                                     # p2p_icp_result.status: a non-finite source or target xyz
@@ -216,6 +232,11 @@ def _stale_reason_of(L):
                                    IcpInput, IcpParams, IcpResult, RefineResult)):
         if L.p2p_abi_sizeof(which) != C.sizeof(typ):
             return "sizeof(%s) = %d in the library, %d in the binding" % (typ.__name__, L.p2p_abi_sizeof(which), C.sizeof(typ))
+    L.p2p_train_sizeof.restype = C.c_int
+    L.p2p_train_sizeof.argtypes = [C.c_int]
+    for which, typ in enumerate((TrainDraw, TrainColour)):
+        if L.p2p_train_sizeof(which) != C.sizeof(typ):
+            return "sizeof(%s) = %d in the library, %d in the binding" % (typ.__name__, L.p2p_train_sizeof(which), C.sizeof(typ))
     return None
 
 
@@ -306,6 +327,9 @@ def lib():
     L.p2p_render_xyz_batch.argtypes = [vp, C.POINTER(vp), ci, C.POINTER(RefineJob), ci, ci, ci, vp, vp, vp]
     L.p2p_xyz_patch_batch.argtypes = [vp, C.POINTER(vp), vp, vp, vp, ci, ci, ci, ci, vp, vp]
     L.p2p_xyz_rotate_patch_batch.argtypes = [vp, C.POINTER(vp), vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp]
+    L.p2p_train_sizeof.argtypes = [ci]
+    L.p2p_train_batch.argtypes = [vp, ci, C.POINTER(vp), vp, C.POINTER(vp), vp, C.POINTER(TrainDraw), C.POINTER(TrainColour), ci, ci,
+                                  vp, vp, vp, ci, vp]
     _lib = L
     return L
 

@@ -216,6 +216,7 @@ struct Pipeline {
     struct XyzWork { DevBuf key, color, depth, bbox, jobs; } xyz;
     struct PatchWork { DevBuf rgb, color, depth, jobs, range, out, cv, cv_tmp, items, weights, frange; } patch;      // p2p_xyz_patch_batch (xyz_patch.hip)
     struct RotWork { DevBuf lv, tabs, rng, items, box, crop; } rot;      // p2p_xyz_rotate_patch_batch (xyz_patch.hip); frames and slots live in patch
+    struct TrainWork { DevBuf samples, patch, bg, aug, mk, img, imgv, cv, dl, base, rot, aav, out; PinnedBuf stage, h_out; } train;      // p2p_train_batch (train_batch.hip)
     ~Pipeline();
 };
 

@@ -685,6 +685,183 @@ def xyz_rotate_patch_batch(ctx: Context, rgbs, color, depth, angles, generation:
     return res
 
 
+def train_frame_shape(patch_shape, back_shape):
+    """(rows, columns) of the background after data_io.py:78-85: an axis shorter than twice the patch is stretched to twice the patch."""
+    ph, pw = int(patch_shape[0]), int(patch_shape[1])
+    H, W = int(back_shape[0]), int(back_shape[1])
+    if H < 2 * ph or W < 2 * pw:
+        return max(2 * ph if H < 2 * ph else 0, H), max(2 * pw if W < 2 * pw else 0, W)
+    return H, W
+
+
+def train_rotate_matrix(side: int, angle: float):
+    """Rows 0 and 1 (6 doubles) of what skimage.transform.rotate(image [side, side], angle) -- no resize -- hands to its warp:
+    t1 @ (t2 @ t3) in that association, as skimage_rotate_matrix forms it before its corner step."""
+    def translation(tx, ty):
+        m = np.array([[1.0, -0.0, 0], [0.0, 1.0, 0], [0, 0, 1]])
+        m[0:2, 2] = (tx, ty)
+        return m
+    a = np.deg2rad(angle)
+    center = np.array((side, side)) / 2. - 0.5
+    t2 = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]])
+    m = _rot_mm(translation(*center), _rot_mm(t2, translation(*(-center))))
+    return m[:2].ravel()
+
+
+def train_draws(rand, patch_shape, back_shape, batch_count: int):
+    """One sample's draws of data_io.py: get_patch_pair, taken from `rand` (the `random` module or a random.Random: .random() and
+    .gauss()) in the reference's order and turned into integers by the reference's int(...) expressions in Python floats.
+    back_shape: the background's (H, W[, C]), or a callable that receives the first draw (the background index is
+    int(draw * (n_background - 1)), :71) and returns that shape.  -> dict: the fields of p2p_train_draw (rect holds the three
+    rectangles with Python's slice rule applied to the frame), 'frame' (rows, columns after the enlargement rule), 'angle', and
+    'draws', the raw values in the order they were consumed."""
+    raw = []
+
+    def rnd():
+        raw.append(rand.random())
+        return raw[-1]
+    ph, pw = int(patch_shape[0]), int(patch_shape[1])
+    first = rnd()
+    shape = back_shape(first) if callable(back_shape) else back_shape
+    Hb, Wb = train_frame_shape((ph, pw), shape)
+    v_ref = int(rnd() * (Hb - ph - 20) + 10)
+    u_ref = int(rnd() * (Wb - pw - 20) + 10)
+    box = (v_ref, u_ref, v_ref + ph, u_ref + pw)
+    ct_v = int((box[0] + box[2]) / 2 + (rnd() * 10 - 5))
+    ct_u = int((box[1] + box[3]) / 2 + (rnd() * 10 - 5))
+    width = (box[3] - box[1]) * (1 + (rnd() * 0.6 - 0.3))
+    height = (box[2] - box[0]) * (1 + (rnd() * 0.6 - 0.3))
+    h = w = max(width * 1.5, height * 1.5)
+    v1, v2, u1, u2 = ct_v - int(h / 2), ct_v + int(h / 2), ct_u - int(w / 2), ct_u + int(w / 2)
+    side = v2 - v1
+    shift_v = shift_u = 0
+    if v1 < 0:
+        shift_v, v1 = abs(v1), 0
+    v2 = min(v2, Hb)
+    if u1 < 0:
+        shift_u, u1 = abs(u1), 0
+    u2 = min(u2, Wb)
+
+    def rectangle(low):
+        h_aug = int((rnd() * 0.5 + low) * h)
+        w_aug = int((rnd() * 0.5 + low) * w)
+        ratio = 0.5
+        d_v = int(int((box[0] + box[2]) / 2) + (rnd() * ratio * 2 - ratio) * height)
+        d_u = int(int((box[1] + box[3]) / 2) + (rnd() * ratio * 2 - ratio) * width)
+        if not (h_aug > 0 and w_aug > 0):
+            return [0, 0, 0, 0]
+        r0, r1, _ = slice(d_v, d_v + h_aug).indices(Hb)
+        c0, c1, _ = slice(d_u, d_u + w_aug).indices(Wb)
+        return [r0, r1, c0, c1] if r0 < r1 and c0 < c1 else [0, 0, 0, 0]
+    rect = [rectangle(0.2), [0, 0, 0, 0], [0, 0, 0, 0]]
+    sigma_edge = rnd() * 2
+    sigma_blur = rnd() * 2
+    even = batch_count % 2 == 0
+    sigma_ran = 0.0
+    if even:
+        raw.append(rand.gauss(0.5, 0.3))
+        sigma_ran = min(max(raw[-1], 0.1), 1.0)
+        rect[1] = rectangle(0.0)
+        rect[2] = rectangle(0.0)
+    angle = rnd() * 30 - 15
+    return {"v_ref": v_ref, "u_ref": u_ref, "v1": v1, "v2": v2, "u1": u1, "u2": u2, "side": side, "shift_v": shift_v, "shift_u": shift_u,
+            "rect": rect, "even": int(even), "sigma_edge": sigma_edge, "sigma_blur": sigma_blur, "sigma_ran": sigma_ran, "angle": angle,
+            "rot": train_rotate_matrix(side, angle) if side > 0 else np.full(6, np.nan), "frame": (Hb, Wb), "draws": raw}
+
+
+TRAIN_COLOUR_IDS = ("add0", "add1", "add2", "contrast", "multiply", "blur", "noise", "contrast2")
+
+
+def train_colours(rng, n: int, first_sample: int = 0):
+    """n parameter records of the colour stage (seq_syn, data_io.py:42-51) from a numpy.random.Generator: a random order of the eight
+    augmenters and imgaug's documented parameter ranges.  An explicitly unpinned restatement: imgaug's own random stream and float
+    arithmetic are not reproduced.  -> list of dicts with the fields of p2p_train_colour."""
+    out = []
+    for k in range(n):
+        rec = {"order": [int(v) for v in rng.permutation(8)], "add": [float(v) for v in rng.uniform(-15, 15, 3)],
+               "contrast": float(rng.uniform(0.8, 1.3))}
+        rec["mul"] = [float(v) for v in rng.uniform(0.8, 1.2, 3)] if rng.random() < 0.5 else [float(rng.uniform(0.8, 1.2))] * 3
+        rec["blur_sigma"] = float(rng.uniform(0.0, 0.5))
+        rec["noise_scale"] = 10.0 if rng.random() < 0.1 else 0.0
+        if rng.random() < 0.5:
+            rec["contrast2"] = [float(v) for v in rng.uniform(0.5, 2.2, 3)] if rng.random() < 0.3 else [float(rng.uniform(0.5, 2.2))] * 3
+        else:
+            rec["contrast2"] = [1.0, 1.0, 1.0]
+        rec["sample"] = first_sample + k
+        rec["seed"] = int(rng.integers(0, 2 ** 63))
+        out.append(rec)
+    return out
+
+
+def train_patch_batch(ctx: Context, patches, backgrounds, draws, colours=None, imsize: int = 128, device: bool = False,
+                      return_status: bool = False, generation: int = 1):
+    """A batch of training samples in one library call (p2p_train_batch; data_io.py: get_patch_pair for scikit-image 0.17 / 0.18).
+    patches: uint8 [h, w, 6 or 7] arrays as make_train_xyz writes them (h, w <= 128); backgrounds: uint8 [H, W, 3] or [H, W], one per
+    sample (the same array may appear many times); draws: the records of train_draws; colours: None (the colour stage is skipped) or
+    the records of train_colours -- that stage follows imgaug's documented meaning and is not pinned to it.
+    -> (src [n, S, S, 3], tgt [n, S, S, 3], mask [n, S, S]) float32, S = imsize: numpy arrays, or with device=True torch tensors on
+    the context's device that the kernels wrote directly.  A sample the library leaves out (a patch above 128, a background smaller
+    than the patch plus 20 after the enlargement rule, a draw that is not finite or a window above 250) raises ValueError; with
+    return_status=True its outputs are 0 and the int32 status array is returned as a fourth value."""
+    n = len(patches)
+    if len(backgrounds) != n or len(draws) != n or (colours is not None and len(colours) != n):
+        raise ValueError("patches / backgrounds / draws / colours do not describe %d samples" % n)
+    S = int(imsize)
+    patches = [np.ascontiguousarray(p, dtype=np.uint8) for p in patches]
+    backgrounds = [np.ascontiguousarray(b, dtype=np.uint8) for b in backgrounds]
+    if any(p.ndim != 3 for p in patches) or any(b.ndim not in (2, 3) for b in backgrounds):
+        raise ValueError("a patch must be [h, w, c] and a background [H, W, 3] or [H, W]")
+    pshape = np.array([p.shape for p in patches], np.int32).reshape(n, 3)
+    bshape = np.array([b.shape if b.ndim == 3 else b.shape + (1,) for b in backgrounds], np.int32).reshape(n, 3)
+    dr = (_lib.TrainDraw * max(1, n))()
+    for k, d in enumerate(draws):
+        r = dr[k]
+        for f in ("v_ref", "u_ref", "v1", "v2", "u1", "u2", "side", "shift_v", "shift_u", "even"):
+            setattr(r, f, int(d[f]))
+        for q in range(3):
+            for e in range(4):
+                r.rect[q][e] = int(d["rect"][q][e])
+        r.sigma_edge, r.sigma_blur, r.sigma_ran = float(d["sigma_edge"]), float(d["sigma_blur"]), float(d["sigma_ran"])
+        for q in range(6):
+            r.rot[q] = float(d["rot"][q])
+    co = None
+    if colours is not None:
+        co = (_lib.TrainColour * max(1, n))()
+        for k, d in enumerate(colours):
+            r = co[k]
+            for q in range(8):
+                r.order[q] = int(d["order"][q])
+            for q in range(3):
+                r.add[q], r.mul[q], r.contrast2[q] = float(d["add"][q]), float(d["mul"][q]), float(d["contrast2"][q])
+            r.contrast, r.blur_sigma, r.noise_scale = float(d["contrast"]), float(d["blur_sigma"]), float(d["noise_scale"])
+            r.sample, r.seed = int(d["sample"]) & 0xffffffff, int(d["seed"]) & 0xffffffffffffffff
+    pp = (C.c_void_p * max(1, n))(*[p.ctypes.data for p in patches])
+    bp = (C.c_void_p * max(1, n))(*[b.ctypes.data for b in backgrounds])
+    status = np.zeros(max(1, n), np.int32)
+    if device:
+        import torch
+        dev = torch.device("cuda", ctx.device)
+        src = torch.empty((n, S, S, 3), dtype=torch.float32, device=dev)
+        tgt = torch.empty((n, S, S, 3), dtype=torch.float32, device=dev)
+        mask = torch.empty((n, S, S), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        ptrs = (src.data_ptr(), tgt.data_ptr(), mask.data_ptr())
+    else:
+        src, tgt, mask = np.zeros((n, S, S, 3), np.float32), np.zeros((n, S, S, 3), np.float32), np.zeros((n, S, S), np.float32)
+        ptrs = (src.ctypes.data, tgt.ctypes.data, mask.ctypes.data)
+    _lib.check(_lib.lib().p2p_train_batch(ctx.handle, n, pp, pshape.ctypes.data, bp, bshape.ctypes.data, dr, co, S, int(generation),
+                                          ptrs[0], ptrs[1], ptrs[2], _lib.MEM_DEVICE if device else _lib.MEM_HOST, status.ctypes.data),
+               "p2p_train_batch")
+    status = status[:n]
+    if return_status:
+        return src, tgt, mask, status
+    if n and status.any():
+        msg = _lib.lib().p2p_last_error()
+        raise ValueError("train_patch_batch: samples %s were left out (status %s): %s"
+                         % (np.nonzero(status)[0].tolist(), status[status != 0].tolist(), msg.decode() if msg else "?"))
+    return src, tgt, mask
+
+
 def depth_score_batch(ctx: Context, meshes, depths, jobs, inlier_masks: bool = False):
     """Depth agreement at each job's pose (p2p_depth_score_batch; icp3d.py:470-490): renders the job and compares it with
     depths[job['image']] (float32 metres, depth_scale already applied) over job['union_mask'].  Returns a list of dicts
